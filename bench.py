@@ -7,9 +7,15 @@ one 64-image batch per GPU.  N>1: launched by torch.distributed.run, one rank pe
 weak scaling (64 images per rank), exact global-mean CE.
 
 Prints ONE JSON line (rank 0).  `roofline` is the whole train step on the MFMA roof
-(519.9157 GFLOP per 64-image step), plus the step's dominant kernel class timed in
-the step (in-kernel timestamps);
-`cpu_baseline` times the CPU oracle (fp32 eager torch, train mode) on this host.
+(519.9157 GFLOP per 64-image step).  A plain run sets up, warms up, times
+`--steps` steps and prints the line; `--dump-outputs DIR` also writes what a step of the timed path
+computes (the loss and a fixed sample of every updated parameter) as DIR/<name>.npy -- of one step
+from the initial state, which is the same in every run (dump_outputs says why not of the last one).
+
+`--full` adds the secondary measurements, each a run of its own after the timed region: the
+host-batch rate (`host_batches`), the step's dominant kernel class timed in the step (in-kernel
+timestamps, `dominant_kernel`), and `cpu_baseline`, which times the CPU oracle (fp32 eager torch,
+train mode) on this host.
 """
 import argparse
 import json
@@ -163,6 +169,36 @@ def host_batches(eng, cfg, dev, steps=20, warmup=5):
                                     "double-buffered staging, side-stream H2D, PCIe inclusive)"}
 
 
+DUMP_SAMPLE = 65536  # elements kept of one parameter tensor (about 27 MB of f32 in all at C2)
+
+
+def dump_outputs(eng, loss, directory):
+    """What a caller of the timed path holds after a step: the step's loss (`loss.npy`) and the
+    parameters the step left behind (`param.<reference name>.npy`, f32).  The C2 model is 220 MB of f32,
+    so a tensor larger than DUMP_SAMPLE elements is written as a fixed sample: the elements at sorted
+    indices drawn without replacement from a generator seeded with the CRC-32 of the tensor's name
+    (the same indices in every run and every build).
+
+    main() calls it on a second engine that has run the timed path ONCE from the run's initial state
+    (same weights, same batch, same dropout seed), not on the timed engine: one step is the same from
+    run to run up to the last bit of the LayerNorm / bias / embedding gradients' f32 atomic sums
+    (measured: loss bit-identical, 30 of 191 tensors off by at most one f32 ulp), while consecutive
+    steps are not comparable -- Adam turns a noise-level gradient into a full +-lr move, so after
+    2 + 3 steps two runs of one build already differ by 1.2e-3 in single weights (2.4 lr) and after
+    10 + 50 steps by 1.5e-2 and 6e-4 in the loss (`final_loss` in the result line is that value)."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "loss.npy"), loss.detach().float().cpu().numpy())
+    for name, t in eng.state_dict(with_buffer=False).items():
+        a = t.numpy().reshape(-1)
+        if a.size > DUMP_SAMPLE:
+            r = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a[np.sort(r.choice(a.size, size=DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(directory, f"param.{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -170,9 +206,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--graph", action="store_true", help="replay the step as one hipGraph (slower on ROCm 7)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure host_batches, dominant_kernel and cpu_baseline "
+                         "(one GPU only; each is a run of its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what one step of the timed path computes from the initial "
+                         "state (loss, sampled updated parameters; the same in every run) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--cpu-steps", type=int, default=5)
-    ap.add_argument("--no-host-batches", action="store_true", help="skip the secondary host-batch line")
+    ap.add_argument("--no-host-batches", action="store_true", help="with --full: skip the secondary host-batch line")
     ap.add_argument("--dp1", action="store_true",
                     help="diagnostic: run the engine's RCCL data-parallel step at world size 1 (its collectives and, with CAPGEN_ZERO=2, the sharded update) to price the DP machinery on one GPU")
     args = ap.parse_args()
@@ -193,9 +235,14 @@ def main():
         dist.init_process_group("nccl", device_id=dev)
 
     cfg = preset("C2", dtype=args.dtype, dropout=0.3)   # config.py:61 DROPOUT; attention 0.1
-    eng = Engine(cfg, dev)
-    eng.load_state_dict({k: torch.from_numpy(v) for k, v in reference_init_state_dict(cfg, seed=0).items()})
-    eng.set_graph(args.graph)
+
+    def make_engine():
+        e = Engine(cfg, dev)
+        e.load_state_dict({k: torch.from_numpy(v) for k, v in reference_init_state_dict(cfg, seed=0).items()})
+        e.set_graph(args.graph)
+        return e
+
+    eng = make_engine()
     if world > 1 or args.dp1:
         from capgen.dp import init_engine_dp
         init_engine_dp(eng, rank, world)
@@ -252,6 +299,16 @@ def main():
         dp["global_loss"] = round(final_loss, 6)
         dp["loss_equal_across_ranks"] = bool(lt[0].item() == -lt[1].item())
 
+    if args.dump_outputs and rank == 0:
+        # one step of the timed path from the initial state, on an engine of its own (rank 0's batch,
+        # no communicator): see dump_outputs for why not the timed engine's K-th step
+        ref_eng, ref_loss = make_engine(), torch.zeros(1, device=dev)
+        ref_eng.train_step_raw(f, ft, p, c, B, N, T, ref_loss)
+        torch.cuda.synchronize()
+        dump_outputs(ref_eng, ref_loss, args.dump_outputs)
+        ref_eng.close()
+        del ref_eng
+
     images = B * world * args.steps
     value = images / elapsed
     ms = elapsed / args.steps * 1e3
@@ -285,7 +342,7 @@ def main():
         # not the GPU, sets the step time
         "host_issue_ms_per_step": round(issue_s / args.steps * 1e3, 4),
     }
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_host_batches:
             out["host_batches"] = host_batches(eng, cfg, dev)
         # (runs stamped train steps: after everything else that uses the engine)

@@ -145,7 +145,8 @@ RL_WEIGHTS = dict(structure_loss_weight=0.5, cider_reward_weight=1.0, bleu_rewar
                   entropy_reward_weight=1.0, self_cider_reward_weight=1.0)
 
 
-def make_rl_fixture(tag, cfg, B, N, T, seed, min_valid=None, pad_frac=0.0, store_inputs=True):
+def make_rl_fixture(tag, cfg, B, N, T, seed, min_valid=None, pad_frac=0.0, store_inputs=True,
+                    store_relu_masks=False):
     """pad_frac > 0: raise the classifier bias of the pad id so that about that fraction of the
     argmax samples are 0 (exercises the structure-loss mask; the boost is stored as
     `pad_bias_boost` and applied to the fixture weights by the tests).  store_inputs=False (the
@@ -229,7 +230,22 @@ def make_rl_fixture(tag, cfg, B, N, T, seed, min_valid=None, pad_frac=0.0, store
                    batch_min_valid=np.int64(-1 if min_valid is None else min_valid))
     for k, v in RL_WEIGHTS.items():
         out[k] = np.float64(v)
+    hooks = []
+    if store_relu_masks:
+        # the ReLU pattern the reference differentiates: a pre-activation within fp32 rounding of zero
+        # lands on either side depending on the host's GEMM kernels, and one such unit moves whole
+        # gradient tensors by more than the tests' bound, so the pattern is part of the recorded result
+        def record(prefix):
+            def hook(m, i, o):
+                out[f"relu_mask.{prefix}"] = np.packbits((o.detach() > 0).numpy().reshape(-1))
+                out[f"relu_shape.{prefix}"] = np.array(o.shape, dtype=np.int64)
+            return hook
+        for name, mod in model.named_modules():
+            if name.endswith(".feed_forward.position_wise_1"):
+                hooks.append(mod.register_forward_hook(record(name[:-len(".position_wise_1")])))
     logits = model(object_features=feats, position_features=pos, target_caption=caps)
+    for h in hooks:
+        h.remove()
     seq, logp = model.sample(output=logits)
     loss = crit(model_output=logits.cpu(), sample_sequence=seq.cpu(), sample_logprobs=logp.cpu(), target=caps)
     loss["loss"].mean().backward()
@@ -316,6 +332,10 @@ RL_FIXTURES = {
     # the C5 model itself (6+6 blocks, d=512, h=8, 36 regions, T=20) at the c2s vocabulary
     "c5_rl_c2s": (preset("C2", num_vocab=1000), 4, 36, 20, 12, 12, 0.2),
 }
+# fixtures that also record the reference's ReLU pattern (relu_mask.<feed_forward prefix>, bit-packed):
+# c5_rl_c2s has a unit in encoder block 4 whose pre-activation is 5.9e-7 in float64 and whose sign
+# alone moves encoder.encoder.2's q_linear gradient by 2.2e-4 of its abs-sum
+RL_RELU_MASKS = {"c5_rl_c2s"}
 # C5's own shape (SCST on the C2 model, 64 images per GPU, V=10000); inputs regenerated
 RL_FIXTURES_SEEDED = {
     "c5_rl_c5": (preset("C2"), 64, 36, 20, 13, None, 0.2),
@@ -347,7 +367,7 @@ def main(tags=None):
     for tag, (cfg, B, N, T, seed, mv, pf) in RL_FIXTURES.items():
         if tags and tag not in tags:
             continue
-        make_rl_fixture(tag, cfg, B, N, T, seed, min_valid=mv, pad_frac=pf)
+        make_rl_fixture(tag, cfg, B, N, T, seed, min_valid=mv, pad_frac=pf, store_relu_masks=tag in RL_RELU_MASKS)
     for tag, (cfg, B, N, T, seed, mv, pf) in RL_FIXTURES_SEEDED.items():
         if tags and tag not in tags:
             continue

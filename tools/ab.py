@@ -39,7 +39,7 @@ def main():
             e = dict(os.environ)
             e.update(env)
             cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--steps", str(args.steps), "--warmup",
-                   str(args.warmup), "--no-cpu-baseline", "--no-host-batches"]
+                   str(args.warmup), "--full", "--no-cpu-baseline", "--no-host-batches"]
             p = subprocess.run(cmd, env=e, cwd=REPO, capture_output=True, text=True, timeout=args.timeout)
             if p.returncode != 0:
                 print(f"[{name}] round {r}: rc {p.returncode}\n{p.stderr[-2000:]}", flush=True)

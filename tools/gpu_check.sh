@@ -19,7 +19,7 @@ for step in "$@"; do
       timeout -k 10 200 python -u -c 'import __graft_entry__ as g; g.smoke()' > "$out/smoke.log" 2>&1
       rc=$?; tail -2 "$out/smoke.log"; echo "[smoke rc $rc]"; fatal $rc && exit $rc ;;
     bench)
-      timeout -k 10 300 python -u bench.py > "$out/bench.json" 2> "$out/bench.err"
+      timeout -k 10 300 python -u bench.py --full >"$out/bench.json" 2> "$out/bench.err"
       rc=$?; cut -c1-600 "$out/bench.json"; echo "[bench rc $rc]"; fatal $rc && exit $rc ;;
     ab:*)
       arms=${step#ab:}

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 tag=${1:-r02}
 out=gpurun_out/$tag
 rm -rf "$out" && mkdir -p "$out"
-timeout -k 10 300 python -u bench.py > "$out/bench.json" 2> "$out/bench.err" || { tail -20 "$out/bench.err"; exit 1; }
+timeout -k 10 300 python -u bench.py --full >"$out/bench.json" 2> "$out/bench.err" || { tail -20 "$out/bench.err"; exit 1; }
 cut -c1-400 "$out/bench.json"; echo
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- \
   python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-batches > "$out/trace.log" 2>&1 || { tail -20 "$out/trace.log"; exit 1; }
