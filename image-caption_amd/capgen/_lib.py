@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CAPGEN_LIB_PATH") or os.path.join(_HERE, "libcapgen.so")  # (diagnostic builds)
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 F32, BF16 = 0, 1
 
@@ -91,6 +91,42 @@ _SIGS = {
                                                 _P, _P, _P, _P]),
     "capgen_debug_qkv_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
     "capgen_debug_cross_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "capgen_debug_layernorm_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, C.c_float, C.c_int, C.c_uint64, _P, _P,
+                                             C.c_int, _P, _P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "capgen_debug_layernorm_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int, _P,
+                                             C.c_float, C.c_int, C.c_uint64, _P, _P, _P, _P, _P, C.c_int, C.c_int64,
+                                             _P]),
+    "capgen_debug_column_sum": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int64, C.c_float, _P, _P, C.c_int,
+                                          C.c_int64, _P]),
+    "capgen_debug_stripe_reduce": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, _P]),
+    "capgen_debug_embedding_gather": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "capgen_debug_embedding_scatter_add": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "capgen_debug_pack_encoder_input": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P,
+                                                  _P, C.c_int, C.c_int, _P, _P]),
+    "capgen_debug_prepare_captions": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "capgen_debug_cross_entropy_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
+    "capgen_debug_ce_finish": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "capgen_debug_loss_finalize": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P]),
+    "capgen_debug_adam": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P,
+                                    C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                    C.POINTER(_P), _P]),
+    "capgen_debug_to_bf16": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "capgen_debug_arena_checksum": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_uint64), _P]),
+    "capgen_debug_argmax_softmax": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int,
+                                              _P]),
+    "capgen_debug_slab_argmax": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, _P]),
+    "capgen_debug_beam_step_topk": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
+                                              _P, _P]),
+    "capgen_debug_beam_slab_step": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
+                                              _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "capgen_debug_rl_rows": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "capgen_debug_rl_image": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "capgen_debug_rl_numer": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "capgen_debug_rl_loss": (C.c_int, [_P, _P, C.c_float, _P, _P, _P]),
+    "capgen_debug_rl_grad": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P,
+                                       C.c_int, _P]),
+    "capgen_debug_gemm_classifier": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64,
+                                               _P, _P, C.c_int64, _P, _P, _P]),
     "capgen_dp_unique_id": (C.c_int, [C.c_char_p]),
     "capgen_dp_init": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int]),
     "capgen_dp_set_global_count": (C.c_int, [_P, C.c_float]),

@@ -2735,6 +2735,250 @@ int capgen_debug_gemm_variant(int v) {
   return guarded([&] { gemm_set_variant(v); });
 }
 
+// ---- test hooks of the row-wise / loss / Adam / selection / SCST launchers (ops.h, rl.h) ----
+namespace {
+// the dropout descriptor of a hook: p <= 0 is dropout off; otherwise the 64-bit seed goes to a
+// device word (as the engine's step seed) that lives until the launch has run
+struct HookDrop {
+  uint64_t* dev = nullptr;
+  Drop d{};
+  HookDrop(float p, int site, uint64_t seed, hipStream_t s) {
+    if (!(p > 0.f)) return;
+    require(p < 1.f, "debug hook: dropout p must be in [0, 1)");
+    CAPGEN_HIP(hipMalloc(&dev, 8));
+    CAPGEN_HIP(hipMemcpyAsync(dev, &seed, 8, hipMemcpyHostToDevice, s));
+    CAPGEN_HIP(hipStreamSynchronize(s));  // (the source is a stack word)
+    d.seed_ptr = dev, d.site = (uint32_t)site, d.thresh = drop_threshold(p), d.scale = 1.f / (1.f - p);
+  }
+  void finish(hipStream_t s) {
+    if (!dev) return;
+    CAPGEN_HIP(hipStreamSynchronize(s));
+    uint64_t* p = dev;
+    dev = nullptr;
+    CAPGEN_HIP(hipFree(p));
+  }
+  ~HookDrop() {
+    if (dev) (void)hipFree(dev);  // (error path: hipFree waits for the device)
+  }
+};
+}  // namespace
+
+int capgen_debug_layernorm_fwd(int dtype, int M, int d, const void* a, const float* a_bias, float drop_p,
+                               int drop_site, uint64_t drop_seed, const void* res, const float* pe, int pe_L,
+                               const float* gamma, const float* beta, const int32_t* ids, int64_t ids_ld, int pad_idx,
+                               const unsigned char* valid, void* y, void* v_save, float* mean, float* rstd,
+                               void* stream) {
+  return guarded([&] {
+    const hipStream_t s = (hipStream_t)stream;
+    require(a && gamma && beta && y, "debug_layernorm_fwd: a, gamma, beta, y are required");
+    HookDrop hd(drop_p, drop_site, drop_seed, s);
+    LnFwd f;
+    f.M = M, f.d = d, f.a = a, f.a_bias = a_bias, f.drop = hd.d, f.res = res, f.pe = pe, f.pe_L = pe_L;
+    f.gamma = gamma, f.beta = beta, f.mask.ids = ids, f.mask.ids_ld = ids_ld, f.mask.pad_idx = pad_idx;
+    f.mask.valid = valid, f.y = y, f.v_save = v_save, f.mean = mean, f.rstd = rstd;
+    layernorm_fwd(f, dt(dtype), s);
+    hd.finish(s);
+  });
+}
+
+int capgen_debug_layernorm_bwd(int dtype, int M, int d, const void* dy, const void* v, const float* mean,
+                               const float* rstd, const float* gamma, const int32_t* ids, int64_t ids_ld, int pad_idx,
+                               const unsigned char* valid, float drop_p, int drop_site, uint64_t drop_seed,
+                               void* d_res, void* d_a, float* dgamma, float* dbeta, float* dbias, int stripes,
+                               int64_t stripe_stride, void* stream) {
+  return guarded([&] {
+    const hipStream_t s = (hipStream_t)stream;
+    require(dy && v && mean && rstd && gamma, "debug_layernorm_bwd: dy, v, mean, rstd, gamma are required");
+    require((dgamma == nullptr) == (dbeta == nullptr), "debug_layernorm_bwd: dgamma and dbeta go together");
+    require(stripes >= 1 && (stripes == 1 || stripe_stride >= d), "debug_layernorm_bwd: stripes >= 1, stride >= d");
+    HookDrop hd(drop_p, drop_site, drop_seed, s);
+    LnBwd b;
+    b.M = M, b.d = d, b.dy = dy, b.v = v, b.mean = mean, b.rstd = rstd, b.gamma = gamma;
+    b.mask.ids = ids, b.mask.ids_ld = ids_ld, b.mask.pad_idx = pad_idx, b.mask.valid = valid, b.drop = hd.d;
+    b.d_res = d_res, b.d_a = d_a, b.dgamma = dgamma, b.dbeta = dbeta, b.dbias = dbias;
+    b.stripes = stripes, b.stripe_stride = stripe_stride;
+    layernorm_bwd(b, dt(dtype), s);
+    hd.finish(s);
+  });
+}
+
+int capgen_debug_column_sum(int dtype, const void* X, int M, int N, int64_t ldx, float alpha, const float* alpha_ptr,
+                            float* db, int stripes, int64_t stripe_stride, void* stream) {
+  return guarded([&] {
+    require(stripes >= 1 && ldx >= N, "debug_column_sum: stripes >= 1, ldx >= N");
+    column_sum(X, M, N, ldx, alpha, alpha_ptr, db, dt(dtype), (hipStream_t)stream, stripes, stripe_stride);
+  });
+}
+
+int capgen_debug_stripe_reduce(float* S, int stripes, int64_t stride, int64_t n, float* dst, int accumulate, int clear,
+                               void* stream) {
+  return guarded([&] { stripe_reduce(S, stripes, stride, n, dst, accumulate, (hipStream_t)stream, clear); });
+}
+
+int capgen_debug_embedding_gather(const float* table, const int32_t* ids, int64_t ids_ld, int M, int d, void* out,
+                                  int dtype, void* stream) {
+  return guarded([&] { embedding_gather(table, ids, ids_ld, M, d, out, dt(dtype), (hipStream_t)stream); });
+}
+
+int capgen_debug_embedding_scatter_add(const void* dE, const int32_t* ids, int M, int d, int pad, float* grad,
+                                       int dtype, void* stream) {
+  return guarded([&] { embedding_scatter_add(dE, ids, M, d, pad, grad, dt(dtype), (hipStream_t)stream); });
+}
+
+int capgen_debug_pack_encoder_input(const void* feats, int feats_dtype, const float* pos, int M, int F, int P, int Kp,
+                                    void* out, int out_dtype, unsigned char* valid, const int32_t* img_idx, int N,
+                                    int n_img, uint64_t* seed_bump, void* stream) {
+  return guarded([&] {
+    require(Kp >= F + P, "debug_pack_encoder_input: Kp >= F + P");
+    require(img_idx == nullptr || (N > 0 && M % N == 0), "debug_pack_encoder_input: M must be whole images of N rows");
+    pack_encoder_input(feats, dt(feats_dtype), pos, M, F, P, Kp, out, dt(out_dtype), valid, (hipStream_t)stream,
+                       img_idx, N, n_img, seed_bump);
+  });
+}
+
+int capgen_debug_prepare_captions(const int32_t* caps, int B, int T, int pad, int32_t* ids_in, int32_t* tgt,
+                                  float* count, uint64_t* seed_bump, float* inv_count, void* stream) {
+  return guarded([&] {
+    require(B >= 1 && T >= 2, "debug_prepare_captions: B >= 1, T >= 2");
+    prepare_captions(caps, B, T, pad, ids_in, tgt, count, (hipStream_t)stream, seed_bump, inv_count);
+  });
+}
+
+int capgen_debug_cross_entropy_rows(const float* logits, const int32_t* tgt, int M, int V, int pad, float* loss_row,
+                                    void* dlogits, int dtype, void* stream) {
+  return guarded([&] { cross_entropy_rows(logits, tgt, M, V, pad, loss_row, dlogits, dt(dtype), (hipStream_t)stream); });
+}
+
+int capgen_debug_ce_finish(const void* stats, int64_t ld, const float* tlogit, const int32_t* tgt, int M, int V,
+                           int pad, float* loss_row, void* dl, void* stream) {
+  return guarded([&] {
+    ce_finish(reinterpret_cast<const float2*>(stats), ld, tlogit, tgt, M, V, pad, loss_row,
+              reinterpret_cast<bf16*>(dl), (hipStream_t)stream);
+  });
+}
+
+int capgen_debug_loss_finalize(const float* loss_row, int M, const float* count, int focal, float* loss_out,
+                               float* grad_scale, const float* ce_in, int partial, void* stream) {
+  return guarded([&] { loss_finalize(loss_row, M, count, focal, loss_out, grad_scale, (hipStream_t)stream, ce_in, partial); });
+}
+
+int capgen_debug_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
+                      float eps, int64_t* step, float* scal, void* shadow, int64_t n_shadow, int grid_cap,
+                      int n_tiles, const int64_t* tile_off, const int64_t* tile_len, void* const* tile_dst,
+                      void* stream) {
+  return guarded([&] {
+    const hipStream_t s = (hipStream_t)stream;
+    require(n >= 0 && n_shadow >= 0 && n_shadow <= n, "debug_adam: 0 <= n_shadow <= n");
+    require(n % 4 == 0 && n_shadow % 4 == 0, "debug_adam: n and n_shadow must be multiples of 4");
+    require(n_tiles >= 0 && n_tiles <= AdamTiles::kMax, "debug_adam: at most AdamTiles::kMax tiled ranges");
+    AdamTiles tiles;
+    tiles.n = n_tiles;
+    for (int t = 0; t < n_tiles; ++t)
+      tiles.off[t] = tile_off[t], tiles.len[t] = tile_len[t], tiles.dst[t] = reinterpret_cast<bf16*>(tile_dst[t]);
+    adam_prepare(step, lr, b1, b2, scal, s);
+    adam_update(p, g, m, v, (size_t)n, b1, b2, eps, scal, reinterpret_cast<bf16*>(shadow), (size_t)n_shadow, s,
+                grid_cap, tiles);
+  });
+}
+
+int capgen_debug_to_bf16(const float* src, void* dst, int64_t n, void* stream) {
+  return guarded([&] { to_bf16(src, reinterpret_cast<bf16*>(dst), (size_t)n, (hipStream_t)stream); });
+}
+
+int capgen_debug_arena_checksum(const float* p, int64_t n, uint64_t* out, void* stream) {
+  return guarded([&] {
+    require(out != nullptr && n >= 0, "debug_arena_checksum: null output");
+    *out = arena_checksum(p, (size_t)n, (hipStream_t)stream);
+  });
+}
+
+int capgen_debug_argmax_softmax(const float* logits, int B, int V, int64_t* ids_out, int64_t ids_ld, int col,
+                                int32_t* next_ids, int64_t next_ld, int logsm, void* stream) {
+  return guarded([&] { argmax_softmax(logits, B, V, ids_out, ids_ld, col, next_ids, next_ld, (hipStream_t)stream, logsm); });
+}
+
+int capgen_debug_slab_argmax(const float* logits, const void* stats, int B, int V, int64_t* ids_out, int64_t ids_ld,
+                             int col, int32_t* next_ids, int64_t next_ld, void* stream) {
+  return guarded([&] {
+    slab_argmax(logits, reinterpret_cast<const float2*>(stats), B, V, ids_out, ids_ld, col, next_ids, next_ld,
+                (hipStream_t)stream);
+  });
+}
+
+int capgen_debug_beam_step_topk(const float* logits, const void* stats, const float* prev, int k_in, int B, int V,
+                                int k, int logsm, float* cand_v, int32_t* cand_i, float* out_prob, int32_t* out_src,
+                                int32_t* out_tok, void* stream) {
+  return guarded([&] {
+    const hipStream_t s = (hipStream_t)stream;
+    if (stats)
+      beam_step_topk_slab(logits, reinterpret_cast<const float2*>(stats), prev, k_in, B, V, k, logsm, cand_v, cand_i,
+                          out_prob, out_src, out_tok, s);
+    else
+      beam_step_topk(logits, prev, k_in, B, V, k, logsm, cand_v, cand_i, out_prob, out_src, out_tok, s);
+  });
+}
+
+int capgen_debug_beam_slab_step(const float* logits, const void* stats, const float* prev, int k_in, int B, int V,
+                                int k, int logsm, float* out_prob, int32_t* out_src, int32_t* out_tok,
+                                const int64_t* seq_src, int64_t* seq_dst, int Tw, const int32_t* ids_src,
+                                int32_t* ids_dst, const int32_t* kv_src, int32_t* kv_dst, int Tc, int t, void* stream) {
+  return guarded([&] {
+    require(t >= 0, "debug_beam_slab_step: t >= 0");
+    beam_slab_step(logits, reinterpret_cast<const float2*>(stats), prev, k_in, B, V, k, logsm, out_prob, out_src,
+                   out_tok, seq_src, seq_dst, Tw, ids_src, ids_dst, kv_src, kv_dst, Tc, t, (hipStream_t)stream);
+  });
+}
+
+int capgen_debug_rl_rows(const float* logits, int M, int V, int32_t* sample, float* lse, float* logp_s, float* ent,
+                         void* stream) {
+  return guarded([&] {
+    require(M >= 1 && V >= 1, "debug_rl_rows: M, V >= 1");
+    rl_rows(logits, M, V, sample, lse, logp_s, ent, (hipStream_t)stream);
+  });
+}
+
+int capgen_debug_rl_image(const int32_t* sample, const float* ent, int B, int L, float* ent_img, float* scal,
+                          void* stream) {
+  return guarded([&] { rl_image(sample, ent, B, L, ent_img, scal, (hipStream_t)stream); });
+}
+
+int capgen_debug_rl_numer(const int32_t* sample, const float* logp_s, const float* score, int B, int L, float* scal,
+                          void* stream) {
+  return guarded([&] { rl_numer(sample, logp_s, score, B, L, scal, (hipStream_t)stream); });
+}
+
+int capgen_debug_rl_loss(const float* scal, const float* lm, float w, float* out, float* grad_scale, void* stream) {
+  return guarded([&] { rl_loss(scal, lm, w, out, grad_scale, (hipStream_t)stream); });
+}
+
+int capgen_debug_rl_grad(const float* logits, const int32_t* tgt, const int32_t* sample, const float* lse,
+                         const float* score, const float* count, const float* scal, int B, int L, int V, int pad,
+                         float w, void* dl, int dtype, void* stream) {
+  return guarded([&] {
+    require(B >= 1 && L >= 1 && V >= 1, "debug_rl_grad: B, L, V >= 1");
+    rl_grad(logits, tgt, sample, lse, score, count, scal, B, L, V, pad, w, dl, dt(dtype), (hipStream_t)stream);
+  });
+}
+
+int capgen_debug_gemm_classifier(int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, void* Cp,
+                                 int64_t ldc, const float* bias, void* stats, int64_t stats_ld, const int32_t* ce_tgt,
+                                 float* ce_tlogit, void* stream) {
+  return guarded([&] {
+    require(stats != nullptr, "debug_gemm_classifier: stats is required");
+    gemm_init();
+    GemmArgs ga;
+    ga.M = M, ga.N = N, ga.K = K, ga.A = A, ga.lda = lda, ga.B = B, ga.ldb = ldb, ga.C = Cp, ga.ldc = ldc;
+    ga.bias = bias;
+    if (ce_tgt) {  // training: C = exp(v - slab max) in bf16, the logits are not written
+      ga.ce_stats = reinterpret_cast<float2*>(stats), ga.ce_ld = stats_ld, ga.ce_tgt = ce_tgt, ga.ce_tlogit = ce_tlogit;
+      gemm(ga, DType::BF16, DType::BF16, false, false, (hipStream_t)stream);
+    } else {  // decode: C = the f32 logits
+      ga.dec_stats = reinterpret_cast<float2*>(stats), ga.dec_ld = stats_ld;
+      gemm(ga, DType::BF16, DType::F32, false, false, (hipStream_t)stream);
+    }
+  });
+}
+
 int capgen_debug_copy_buffer(capgen_t* h, int which, void* host_dst, int64_t bytes) {
   return guarded([&] {
     set_device(h);

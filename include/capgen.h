@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define CAPGEN_ABI_VERSION 11
+#define CAPGEN_ABI_VERSION 12
 
 typedef struct capgen_engine capgen_t;
 
@@ -257,6 +257,108 @@ int capgen_debug_cross_attention(int B, int Lq, int Lk, int H, const void* X, co
 int capgen_debug_attention_bwd_wo(int B, int Lq, int Lk, int H, const void* q, const void* k, const void* v,
                                   const unsigned char* key_valid, int causal, const void* dA, const void* Wo, void* dq,
                                   void* dk, void* dv, void* stream);
+
+/* Test hooks: the row-wise, loss, optimizer, selection and SCST launchers (csrc/ops.h, csrc/rl.h),
+ * one launcher per call on raw device pointers and the given stream; the arguments are the
+ * launcher's own (see the formula comments there), optional pointers may be NULL, dtype 0 = f32,
+ * 1 = bf16.  tests/test_gpu_rowops.py compares each with a float64 restatement.
+ * layernorm_fwd: y = LN(drop(a + a_bias) + res + pe[m % pe_L]) * rowmask; v_save = the LN input;
+ * drop_p <= 0 = no dropout, else the hook places drop_seed in a device word for the launch (and
+ * waits for the launch before it frees the word).  Row mask: ids[m * ids_ld] == pad_idx or
+ * valid[m] == 0 zero row m.
+ * layernorm_bwd: d_res = grad wrt the LN input, d_a = that through the same dropout; dgamma / dbeta
+ * / dbias (column sum of d_a) are ACCUMULATED, workgroup w into stripe (w % stripes) * stripe_stride. */
+int capgen_debug_layernorm_fwd(int dtype, int M, int d, const void* a, const float* a_bias, float drop_p,
+                               int drop_site, uint64_t drop_seed, const void* res, const float* pe, int pe_L,
+                               const float* gamma, const float* beta, const int32_t* ids, int64_t ids_ld, int pad_idx,
+                               const unsigned char* valid, void* y, void* v_save, float* mean, float* rstd,
+                               void* stream);
+int capgen_debug_layernorm_bwd(int dtype, int M, int d, const void* dy, const void* v, const float* mean,
+                               const float* rstd, const float* gamma, const int32_t* ids, int64_t ids_ld, int pad_idx,
+                               const unsigned char* valid, float drop_p, int drop_site, uint64_t drop_seed,
+                               void* d_res, void* d_a, float* dgamma, float* dbeta, float* dbias, int stripes,
+                               int64_t stripe_stride, void* stream);
+/* db[s][n] += alpha (* *alpha_ptr) * sum_m X[m][n] (row stride ldx), rows spread over `stripes`
+ * partial sums stripe_stride floats apart; stripe_reduce: dst[i] (+)= sum_s S[s * stride + i],
+ * clear = zero the partials as they are read. */
+int capgen_debug_column_sum(int dtype, const void* X, int M, int N, int64_t ldx, float alpha, const float* alpha_ptr,
+                            float* db, int stripes, int64_t stripe_stride, void* stream);
+int capgen_debug_stripe_reduce(float* S, int stripes, int64_t stride, int64_t n, float* dst, int accumulate, int clear,
+                               void* stream);
+/* out[m] = table[ids[m * ids_ld]] (f32 table -> dtype); grad[ids[m]] += dE[m] for ids[m] != pad. */
+int capgen_debug_embedding_gather(const float* table, const int32_t* ids, int64_t ids_ld, int M, int d, void* out,
+                                  int dtype, void* stream);
+int capgen_debug_embedding_scatter_add(const void* dE, const int32_t* ids, int M, int d, int pad, float* grad,
+                                       int dtype, void* stream);
+/* out[m] = [feats[m] | pos[m] | 0] (width Kp), valid[m] = any(pos[m] != 0); with img_idx ([M / N]) the
+ * rows of image img_idx[b] of an [n_img, N, .] store (out of range: a zero row, valid 0); seed_bump
+ * (optional device u64) advances by 0x9E3779B97F4A7C15 once. */
+int capgen_debug_pack_encoder_input(const void* feats, int feats_dtype, const float* pos, int M, int F, int P, int Kp,
+                                    void* out, int out_dtype, unsigned char* valid, const int32_t* img_idx, int N,
+                                    int n_img, uint64_t* seed_bump, void* stream);
+/* caps [B][T] -> ids_in / tgt [B][T-1], count = #(tgt != pad) (f32), inv_count = 1 / count (optional). */
+int capgen_debug_prepare_captions(const int32_t* caps, int B, int T, int pad, int32_t* ids_in, int32_t* tgt,
+                                  float* count, uint64_t* seed_bump, float* inv_count, void* stream);
+/* loss_row[m] = lse - logit[tgt], dlogits = softmax - onehot (dtype; 0 for tgt == pad).  ce_finish: the
+ * same from the classifier epilogue's outputs (stats = {max, sum exp} float pairs per 16-column slab,
+ * row stride ld pairs; dl bf16 holds exp(v - slab max) and is rewritten in place; V % 4 == 0).
+ * loss_finalize: loss = sum(loss_row) / count, or (1 - e^-ce)^2 ce (focal), grad_scale = dloss / d(row
+ * sum) (optional); ce_in = the mean is given; partial = write the mean only. */
+int capgen_debug_cross_entropy_rows(const float* logits, const int32_t* tgt, int M, int V, int pad, float* loss_row,
+                                    void* dlogits, int dtype, void* stream);
+int capgen_debug_ce_finish(const void* stats, int64_t ld, const float* tlogit, const int32_t* tgt, int M, int V,
+                           int pad, float* loss_row, void* dl, void* stream);
+int capgen_debug_loss_finalize(const float* loss_row, int M, const float* count, int focal, float* loss_out,
+                               float* grad_scale, const float* ce_in, int partial, void* stream);
+/* One torch.optim.Adam step of a flat f32 arena (n % 4 == 0): adam_prepare (++*step, device int64; scal =
+ * 2 device floats) then adam_update; shadow[i] = bf16(p[i]) for i < n_shadow (optional), grid_cap > 0
+ * caps the workgroups, and n_tiles <= 4 ranges [tile_off, tile_off + tile_len) of the shadow (HOST
+ * arrays; whole 16-row blocks of 512-wide rows) are also written to tile_dst[t] in the attention
+ * fronts' tiled layout.  to_bf16: dst = bf16(src).  arena_checksum: sum bits(p[i]) (2 i + 1) mod 2^64
+ * into the HOST word *out (synchronous). */
+int capgen_debug_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
+                      float eps, int64_t* step, float* scal, void* shadow, int64_t n_shadow, int grid_cap,
+                      int n_tiles, const int64_t* tile_off, const int64_t* tile_len, void* const* tile_dst,
+                      void* stream);
+int capgen_debug_to_bf16(const float* src, void* dst, int64_t n, void* stream);
+int capgen_debug_arena_checksum(const float* p, int64_t n, uint64_t* out, void* stream);
+/* Decode selection.  argmax_softmax: ids_out[b * ids_ld + col] (and next_ids[b * next_ld]) = argmax of
+ * the softmax (logsm: log-softmax) of row b, first index on ties; slab_argmax: the same from the decode
+ * classifier's slab stats.  beam_step_topk: per image i the k best prev[j*B+i] + (log-)softmax(row
+ * j*B+i)[v] under (score desc, j*V + v asc) -> out_prob / out_src / out_tok [sel*B + i]; stats NULL =
+ * the full-row kernels, else the slab kernels (V <= 16384); cand_v / cand_i: k_in*B*k scratch.
+ * beam_slab_step: the slab step in one launch, plus the gather of the sequences [.][Tw] (int64), ids
+ * and K/V row table [.][Tc] from the source beams with the token at column t + 1. */
+int capgen_debug_argmax_softmax(const float* logits, int B, int V, int64_t* ids_out, int64_t ids_ld, int col,
+                                int32_t* next_ids, int64_t next_ld, int logsm, void* stream);
+int capgen_debug_slab_argmax(const float* logits, const void* stats, int B, int V, int64_t* ids_out, int64_t ids_ld,
+                             int col, int32_t* next_ids, int64_t next_ld, void* stream);
+int capgen_debug_beam_step_topk(const float* logits, const void* stats, const float* prev, int k_in, int B, int V,
+                                int k, int logsm, float* cand_v, int32_t* cand_i, float* out_prob, int32_t* out_src,
+                                int32_t* out_tok, void* stream);
+int capgen_debug_beam_slab_step(const float* logits, const void* stats, const float* prev, int k_in, int B, int V,
+                                int k, int logsm, float* out_prob, int32_t* out_src, int32_t* out_tok,
+                                const int64_t* seq_src, int64_t* seq_dst, int Tw, const int32_t* ids_src,
+                                int32_t* ids_dst, const int32_t* kv_src, int32_t* kv_dst, int Tc, int t, void* stream);
+/* SCST kernels (csrc/rl.hip): rows = sample (argmax log-softmax), lse, logp[sample], entropy per logit
+ * row; image = per-image masked mean entropy, scal[0] = sum(mask); numer: scal[1] = -sum logp mask
+ * score; loss: out = {(1-w) lm + w struct, lm, struct}; grad = the fully scaled d loss / d logits. */
+int capgen_debug_rl_rows(const float* logits, int M, int V, int32_t* sample, float* lse, float* logp_s, float* ent,
+                         void* stream);
+int capgen_debug_rl_image(const int32_t* sample, const float* ent, int B, int L, float* ent_img, float* scal,
+                          void* stream);
+int capgen_debug_rl_numer(const int32_t* sample, const float* logp_s, const float* score, int B, int L, float* scal,
+                          void* stream);
+int capgen_debug_rl_loss(const float* scal, const float* lm, float w, float* out, float* grad_scale, void* stream);
+int capgen_debug_rl_grad(const float* logits, const int32_t* tgt, const int32_t* sample, const float* lse,
+                         const float* score, const float* count, const float* scal, int B, int L, int V, int pad,
+                         float w, void* dl, int dtype, void* stream);
+/* The classifier GEMM's fused epilogues (bf16 NT, v = A . B^T + bias, A [M][K], B [N][K], f32 bias):
+ * ce_tgt given = the training form (C bf16 = exp(v - slab max), stats = {max, sum exp} per 16-column
+ * slab, ce_tlogit[m] = v[ce_tgt[m]]); ce_tgt NULL = the decode form (C = the f32 logits + stats). */
+int capgen_debug_gemm_classifier(int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, void* Cp,
+                                 int64_t ldc, const float* bias, void* stats, int64_t stats_ld, const int32_t* ce_tgt,
+                                 float* ce_tlogit, void* stream);
 
 /* Persisted GEMM autotune table (no reference counterpart: the reference's GEMMs are cuBLAS calls
  * of torch eager, models.py:120-126).  The bf16 GEMM picks a tile / wave / pipeline / split-K
