@@ -60,6 +60,15 @@ struct Planner {
   }
 };
 
+// a value set for a scope: the old one is put back when the scope ends, also by an exception
+template <class T>
+struct Scoped {
+  T& ref;
+  T old;
+  Scoped(T& r, T v) : ref(r), old(r) { r = v; }
+  ~Scoped() { ref = old; }
+};
+
 struct EncAct {
   void *qkv, *att, *v1, *Y, *H, *v2;
   float *P, *m1, *r1, *m2, *r2;
@@ -130,8 +139,6 @@ struct GenWS {
   int64_t *seq, *seq2;   // beam [R][Tw]
   float *bprob, *bprob2;
   int32_t *bsrc, *btok;
-  int64_t* out_ids;  // staged outputs of a graph-replayed decode: ids [R][maxlen + 1]
-  float* out_attn;   // greedy attention_list [maxlen - 1][R][N]
 };
 
 __global__ void init_gen_ids_kernel(int64_t* out, int rows, int width, int32_t* ids, int tcap) {
@@ -259,13 +266,9 @@ struct capgen_engine {
   }
   void build_dtiles(hipStream_t s) {
     if (!dtiles) return;
-    // skipped while the tiles match the weights (~0.12 ms per greedy / beam call); a build captured
-    // into a graph runs at every replay
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    CAPGEN_HIP(hipStreamIsCapturing(s, &cs));
-    const bool capturing = cs != hipStreamCaptureStatusNone;
-    if (!capturing && dtiles_ver == wver) return;
-    if (!capturing) dtiles_ver = wver;
+    // skipped while the tiles match the weights (~0.12 ms per greedy / beam call)
+    if (dtiles_ver == wver) return;
+    dtiles_ver = wver;
     if (emb_bf) to_bf16(P(L.emb), emb_bf, (size_t)L.V * L.dwe, s);
     for (const auto& t : dtile_list()) {
       auto it = dtile.find(t[0]);
@@ -304,38 +307,6 @@ struct capgen_engine {
   int fwd_graph_mode = knob(Knob::FwdGraph);
   bool fwd_graph_on = fwd_graph_mode != 0;
   hipGraphExec_t fexec = nullptr;
-  // split forward graphs (CAPGEN_FWD_SPLIT=1, with the decoder front on es2): the front and the
-  // critical chain as separate LINEAR graphs on their own streams.  Under rocprofv3 the one
-  // multi-stream graph ran its front branch before the encoder (no overlap) and the split graphs
-  // overlapped, but without the profiler the single graph measured faster (4-round A/B: 3.032 vs
-  // 3.048 ms/step; front off: 3.072).  The multi-branch graph costs the host more to launch
-  // (enqueue per step 2.52 vs 2.27 ms; linear graphs ~0.1 us per node), which matters once the
-  // step also issues the per-bucket collectives.  The single graph is the default at every world
-  // size (faster on the GPU; the count / partial-CE all-reduces capture into it as well);
-  // CAPGEN_FWD_SPLIT=1 selects the split graphs
-  int fwd_split_env = knob(Knob::FwdSplit);
-  bool fwd_split() const { return fwd_split_env == 1; }
-  bool cap_split = false;  // forward() is being captured in split mode: it ends/begins captures
-  hipGraph_t fg[4] = {};   // pre, front, encoder, decoder
-  hipGraphExec_t fx[4] = {};
-  void cap_cut(hipStream_t from, int idx, hipStream_t next) {  // end capture on `from` into fg[idx]
-    CAPGEN_HIP(hipStreamEndCapture(from, &fg[idx]));
-    if (next) CAPGEN_HIP(hipStreamBeginCapture(next, hipStreamCaptureModeThreadLocal));
-  }
-  void launch_fwd(hipStream_t cs) {
-    if (fexec) {
-      CAPGEN_HIP(hipGraphLaunch(fexec, cs));
-      return;
-    }
-    CAPGEN_HIP(hipGraphLaunch(fx[0], cs));
-    dep(cs, es2, ev_ff);
-    CAPGEN_HIP(hipGraphLaunch(fx[1], es2));
-    hz::record(ev_fj, es2);
-    CAPGEN_HIP(hipGraphLaunch(fx[2], cs));
-    hz::wait(cs, ev_fj);
-    CAPGEN_HIP(hipGraphLaunch(fx[3], cs));
-  }
-  bool have_fwd_graph() const { return fexec || fx[3]; }
   struct Key {
     const void *f, *p, *c;
     float* loss;
@@ -409,13 +380,8 @@ struct capgen_engine {
   // issue priority of a launch: kernels on the critical stream run their waves at s_setprio 3 so
   // that the weight-gradient / Adam waves of the side streams sharing their CUs yield the issue
   // slots to them (measured 2.779 / 2.788 vs 2.782 / 2.795 ms/step without, round 4)
-  static constexpr bool prio_on = true;
   hipStream_t crit = nullptr;  // critical stream of the running call (es, or the caller's: direct)
-  int prio(hipStream_t s) const { return prio_on && s == (crit ? crit : es) && es2 != s ? 1 : 0; }
-  // direct steps: once the forward graph exists, train_step runs its
-  // critical path on the CALLER's stream -- no caller -> engine -> caller event round trip per
-  // step; es then waits for the step so the engine's host-side syncs on es still cover it
-  // (measured: 3.165 vs 3.170 ms/step, within noise -- the step-boundary gap is the Adam tail)
+  int prio(hipStream_t s) const { return s == (crit ? crit : es) && es2 != s ? 1 : 0; }
   // fused classifier + cross entropy in the bf16 path (CAPGEN_FUSED_CE=0: logits in f32 + ce_kernel)
   bool fused_ce_on = knob(Knob::FusedCe) != 0;
   bool need_logits = false;  // the next forward must materialise the f32 logits (SCST sampling)
@@ -428,7 +394,6 @@ struct capgen_engine {
   bool defer_loss_on = knob(Knob::DeferLoss) != 0;
   int front_join = knob(Knob::FrontJoin);  // encoder block before which the forward joins the decoder front
   float* pending_loss = nullptr;  // set by train_step: the backward finalises the loss into it on es2
-  static constexpr bool direct_on = true;
 
   // diagnostic in-kernel timestamps (capgen_debug_stamps): every GEMM / LayerNorm / attention
   // launch of a step gets a slot of the ring (forward slots first: a captured forward graph keeps
@@ -749,57 +714,15 @@ struct capgen_engine {
       (void)hipGraphExecDestroy(gexec);
       gexec = nullptr;
     }
-    for (auto& x : fx)
-      if (x) (void)hipGraphExecDestroy(x), x = nullptr;
     if (fexec) {
       (void)hipGraphExecDestroy(fexec);
       fexec = nullptr;
     }
-    drop_gen_graph();
   }
-  void drop_gen_graph() {
-    for (auto& e : gen_graphs) (void)hipGraphExecDestroy(e.second);
-    gen_graphs.clear();
-    gen_seen.clear();
-  }
-
-  // Decoding as one replayed hipGraph: the first call with a given
-  // (kind, inputs, shape) runs eagerly (autotunes the GEMMs, sizes the workspaces), the second
-  // captures the whole encode + T-1 decode steps on the engine stream, later ones replay it.
-  // Outputs are staged in the workspace (g.out_*) and copied to the caller's buffers after
-  // the launch, so a new output tensor per call does not defeat the replay.
-  // decode scoring: false = Softmax, probabilities accumulated over beams (Transformer,
-  // model.py:124-128,183); true = LogSoftmax, log-probabilities (PolicyNetwork, model_RL.py:72,182)
-  bool decode_logsm = false;
-  struct GenKey {
-    int kind;  // 0 greedy, 1 greedy + attention, 2 beam (+ 8: log-softmax scoring)
-    const void *f, *p;
-    int ft, B, N, k;
-    bool operator==(const GenKey& o) const {
-      return kind == o.kind && f == o.f && p == o.p && ft == o.ft && B == o.B && N == o.N && k == o.k;
-    }
-  };
-  // off by default: measured slower than eager issue on MI355X / ROCm 7 (C4 B=256: beam 5
-  // 22.6 vs 21.9 ms, greedy 12.4 vs 11.6 ms, tools/bench_generate.py); CAPGEN_GEN_GRAPH=1 enables
-  bool gen_graph_on = knob(Knob::GenGraph) == 1;
-  static constexpr size_t kGenGraphs = 8;  // cached decode graphs (oldest evicted)
-  std::vector<std::pair<GenKey, hipGraphExec_t>> gen_graphs;
-  std::vector<GenKey> gen_seen;  // keys run eagerly once (next call captures)
+  // body() captured on s into an instantiated graph (the capture is ended, and the graph object
+  // destroyed, whether or not body throws)
   template <class F>
-  void gen_run(const GenKey& k, F&& body, hipStream_t s) {
-    if (!gen_graph_on) return body();
-    for (auto& e : gen_graphs)
-      if (e.first == k) {
-        CAPGEN_HIP(hipGraphLaunch(e.second, s));
-        return;
-      }
-    if (std::find(gen_seen.begin(), gen_seen.end(), k) == gen_seen.end()) {  // first sighting: eager
-      body();
-      gen_seen.push_back(k);
-      if (gen_seen.size() > kGenGraphs) gen_seen.erase(gen_seen.begin());
-      return;
-    }
-    const GenWS saved = g;  // beam's host-side ping-pong swaps are replayed from this state
+  hipGraphExec_t capture(hipStream_t s, F&& body) {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     CAPGEN_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -808,26 +731,26 @@ struct capgen_engine {
     } catch (...) {
       (void)hipStreamEndCapture(s, &graph);
       if (graph) (void)hipGraphDestroy(graph);
-      g = saved;
       throw;
     }
     CAPGEN_HIP(hipStreamEndCapture(s, &graph));
-    g = saved;
-    CAPGEN_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    CAPGEN_HIP(hipGraphDestroy(graph));
-    if (gen_graphs.size() >= kGenGraphs) {
-      (void)hipGraphExecDestroy(gen_graphs.front().second);
-      gen_graphs.erase(gen_graphs.begin());
-    }
-    gen_graphs.emplace_back(k, exec);
-    CAPGEN_HIP(hipGraphLaunch(exec, s));
+    const hipError_t inst = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    CAPGEN_HIP(inst);
+    return exec;
   }
+
+  // decode scoring: false = Softmax, probabilities accumulated over beams (Transformer,
+  // model.py:124-128,183); true = LogSoftmax, log-probabilities (PolicyNetwork, model_RL.py:72,182)
+  bool decode_logsm = false;
 
   // ------------------------------------------------------------------------------------
   // one EncoderBlock (modules.py:146-157) over B sequences of N rows: X -> Xout.  valid != null:
   // key-pad OR causal self-attention mask and the non-pad multiply (model.py:312-328).
+  // keep = false (decoding): nothing is saved for a backward (LayerNorm inputs and statistics,
+  // attention probabilities); the launches are the same
   void enc_layer_fwd(const EncLayerOff& w, EncAct& A, const void* X, void* Xout, int B, int N, const uint8_t* valid,
-                     int layer, bool drop_on, hipStream_t s) {
+                     int layer, bool drop_on, hipStream_t s, bool keep = true) {
     const int Me = B * N, d = L.d, He = L.He, dke = d / He;
     const float p = cfg.dropout, pa = cfg.attention_dropout;
     AttnGeom g;
@@ -839,17 +762,26 @@ struct capgen_engine {
     if (valid) g.key_valid = valid, g.kv_bs = N, g.causal = 1;
     g.temperature = std::sqrt((float)dke);
     g.drop = mk_drop(pa, site(0, layer, 0), drop_on);
-    self_attention(X, w.Wqkv, Me, d, g, A.qkv, A.att, keep_probs(g) ? A.P : nullptr, s);
+    self_attention(X, w.Wqkv, Me, d, g, A.qkv, A.att, keep && keep_probs(g) ? A.P : nullptr, s);
     LnFwd l1;
     l1.M = Me, l1.d = d, l1.a = a.tmp, l1.drop = mk_drop(p, site(0, layer, 1), drop_on), l1.res = X;
-    l1.gamma = P(w.ln1g), l1.beta = P(w.ln1b), l1.y = A.Y, l1.v_save = A.v1, l1.mean = A.m1, l1.rstd = A.r1;
+    l1.gamma = P(w.ln1g), l1.beta = P(w.ln1b), l1.y = A.Y;
+    if (keep) l1.v_save = A.v1, l1.mean = A.m1, l1.rstd = A.r1;
     linear_ln(A.att, d, w.Wo, d, Me, d, d, l1, s);
     linear(A.Y, d, w.W1, d, A.H, L.fe, act, Me, L.fe, d, P(w.b1), 1, s);
     LnFwd l2;
     l2.M = Me, l2.d = d, l2.a = a.tmp, l2.a_bias = P(w.b2), l2.drop = mk_drop(p, site(0, layer, 2), drop_on);
     l2.res = A.Y, l2.gamma = P(w.ln2g), l2.beta = P(w.ln2b), l2.mask.valid = valid;
-    l2.y = Xout, l2.v_save = A.v2, l2.mean = A.m2, l2.rstd = A.r2;
+    l2.y = Xout;
+    if (keep) l2.v_save = A.v2, l2.mean = A.m2, l2.rstd = A.r2;
     linear_ln(A.H, L.fe, w.W2, L.fe, Me, d, L.fe, l2, s);
+  }
+  // the region embedding and the shared norm (model.py:294): a.Aenc -> a.X[0]; keep as above
+  void enc_embed_fwd(int Me, bool keep, hipStream_t s) {
+    LnFwd ln;
+    ln.M = Me, ln.d = L.d, ln.a = a.tmp, ln.gamma = P(L.enc_lng), ln.beta = P(L.enc_lnb), ln.y = a.X[0];
+    if (keep) ln.v_save = a.ev0, ln.mean = a.em0, ln.rstd = a.er0;
+    linear_ln(a.Aenc, L.Kp, L.enc_emb_W, L.Kp, Me, L.d, L.Kp, ln, s);
   }
   static constexpr int kImgLayer = 63;  // dropout-site layer index of encoder.image_encoder
 
@@ -958,38 +890,29 @@ struct capgen_engine {
       if (q_proj) linear(A.D1, dd, w.Wq_c, dd, A.qc, dd, act, Md, dd, dd, nullptr, 0, fs);
     };
     if (front) {
-      if (cap_split) cap_cut(s, 0, es2);
-      else dep(s, es2, ev_ff);
+      dep(s, es2, ev_ff);
       if (caps_front) prepare_captions(caps, B, T, cfg.pad_idx, a.ids, a.tgt, a.count, es2, nullptr, defer ? a.grad_scale : nullptr);
       dec_embed(a.tmpf, es2);
       dec_self_half(0, a.tmpf, es2, true);
-      if (cap_split) cap_cut(es2, 1, s);
-      else hz::record(ev_fj, es2);
+      hz::record(ev_fj, es2);
     }
 
     // ---- encoder (model.py:294-332) ----
-    if (L.has_img) {
-      image_objects_fwd(B, N, drop_on, s);
-    } else {
-      LnFwd ln;
-      ln.M = Me, ln.d = d, ln.a = a.tmp, ln.gamma = P(L.enc_lng), ln.beta = P(L.enc_lnb);
-      ln.y = a.X[0], ln.v_save = a.ev0, ln.mean = a.em0, ln.rstd = a.er0;
-      linear_ln(a.Aenc, L.Kp, L.enc_emb_W, L.Kp, Me, d, L.Kp, ln, s);
-    }
+    if (L.has_img) image_objects_fwd(B, N, drop_on, s);
+    else enc_embed_fwd(Me, /*keep=*/true, s);
     // where the critical stream joins the decoder front (eager / single graph): before encoder block
     // front_join (Le + 1: before the decoder, its first reader)
     const int fj = std::max(0, std::min(front_join, L.Le + 1));
     for (int l = 0; l < L.Le; ++l) {
-      if (front && !cap_split && l == fj) hz::wait(s, ev_fj);
+      if (front && l == fj) hz::wait(s, ev_fj);
       enc_layer_fwd(L.enc[l], a.enc[l], a.X[l], a.X[l + 1], B, N, cfg.encode_mask ? a.valid : nullptr, l, drop_on, s);
     }
-    if (front && !cap_split && fj == L.Le) hz::wait(s, ev_fj);
+    if (front && fj == L.Le) hz::wait(s, ev_fj);
     // cross-attention K/V of every decoder block in one GEMM over the encoder output
     linear(a.X[L.Le], d, L.Wkv_all, d, a.KV, (int64_t)L.Ld * 2 * dd, act, Me, L.Ld * 2 * dd, d, nullptr, 0, s);
 
     // ---- decoder (model.py:419-459) ----
-    if (front && cap_split) cap_cut(s, 2, s);
-    else if (front && fj > L.Le) hz::wait(s, ev_fj);
+    if (front && fj > L.Le) hz::wait(s, ev_fj);
     else if (!front) dec_embed(a.tmp, s);
     const int64_t kvld = (int64_t)L.Ld * 2 * dd;
     for (int l = 0; l < L.Ld; ++l) {
@@ -1627,132 +1550,85 @@ struct capgen_engine {
     pending_loss = loss_deferrable() ? (loss ? loss : a.loss) : nullptr;
     if (pending_loss) last_loss = pending_loss;
   }
+  // one eager forward + backward (dropout off: no RNG advance; no all-reduce, no Adam) so that every
+  // GEMM shape of the step is autotuned outside a capture; its gradients are overwritten by the step
+  void tune_once(const void* f, DType ft, const float* pos, const int32_t* caps, int B, int N, int T, float* loss) {
+    if (tuned(B, N, T)) return;
+    forward(f, ft, pos, caps, B, N, T, loss, /*drop_on=*/false, es);
+    backward(es);
+    hz::host_sync(es);
+    tuned_shapes.push_back({B, N, T});
+  }
+  // CAPGEN_HOST_TIMING=1 (debug build): the mean host time of a step's two halves, every 20 steps
+  using host_clock = std::chrono::steady_clock;
+  double ht_fwd = 0, ht_bwd = 0;
+  int ht_steps = 0;
+  void host_timing(const char* fwd_what, host_clock::time_point t0, host_clock::time_point t1) {
+    if (!fwd_what || knob(Knob::HostTiming) == 0) return;
+    const auto t2 = host_clock::now();
+    ht_fwd += std::chrono::duration<double, std::micro>(t1 - t0).count();
+    ht_bwd += std::chrono::duration<double, std::micro>(t2 - t1).count();
+    if (++ht_steps % 20 == 0) {
+      std::fprintf(stderr, "[capgen host] per step: %s %.1f us, backward enqueue %.1f us\n", fwd_what, ht_fwd / 20,
+                   ht_bwd / 20);
+      ht_fwd = ht_bwd = 0;
+    }
+  }
   void train_step(const void* f, DType ft, const float* pos, const int32_t* caps, int B, int N, int T, float* loss,
                   hipStream_t cs) {
     ensure_acts(B, N, T);
     Key k{f, pos, caps, loss, (int)ft, B, N, T, training, in_idx, in_n_img};
     // (the hazard checker's log runs the eager forward: the graph replays the same launches)
-    const bool fwd_graph = fwd_graph_on && !hz::g_log && (world <= 1 || fwd_graph_mode == 2);
-    if (direct_on && !graph_on && fwd_graph && !count_override && have_fwd_graph() && fkey == k && cs != es) {
-      crit = cs;
-      hz::set_critical(cs);
-      launch_fwd(cs);
-      fB = B, fN = N, fT = T, fwd_drop = training;  // host state forward() would have set
+    // under DP the forward graph holds the count and partial-CE all-reduces (RCCL ops capture);
+    // a host-set global count (capgen_dp_set_global_count) runs the forward eagerly instead --
+    // its pinned-memory copy must stay ordered against the host write
+    const bool fwd_graph =
+        !graph_on && fwd_graph_on && !hz::g_log && (world <= 1 || fwd_graph_mode == 2) && !count_override;
+    // the step's two halves on stream s: fwd (the eager forward, or the forward graph's launch), then the
+    // backward with the bucketed RCCL all-reduce (DP) and Adam
+    auto halves = [&](hipStream_t s, auto&& fwd, const char* timed_as) {
+      const auto t0 = host_clock::now();
+      fwd();
+      const auto t1 = host_clock::now();
+      fB = B, fN = N, fT = T, fwd_drop = training;  // host state forward() sets (a graph launch does not)
       set_pending_loss(loss);
-      backward(cs, /*step_params=*/true);
-      crit = nullptr;
+      backward(s, /*step_params=*/true);
+      host_timing(timed_as, t0, t1);
+    };
+    auto eager_fwd = [&] { forward(f, ft, pos, caps, B, N, T, loss, training, es, /*defer_loss=*/true); };
+    // direct steps: once the forward graph exists, train_step runs its critical path on the CALLER's
+    // stream -- no caller -> engine -> caller event round trip per step; es then waits for the step so
+    // the engine's host-side syncs on es still cover it (measured: 3.165 vs 3.170 ms/step, within
+    // noise -- the step-boundary gap is the Adam tail)
+    if (fwd_graph && fexec && fkey == k && cs != es) {
+      {
+        Scoped<hipStream_t> on_caller(crit, cs);
+        hz::set_critical(cs);
+        halves(cs, [&] { CAPGEN_HIP(hipGraphLaunch(fexec, cs)); }, nullptr);
+      }
       hz::record(ev_out, cs);
       hz::wait(es, ev_out);
       return;
     }
     enter(cs);
-    auto body = [&]() {
-      const bool host_timing = knob(Knob::HostTiming) != 0;  // (debug build)
-      static double tf = 0, tb = 0;
-      static int nsteps = 0;
-      auto t0 = std::chrono::steady_clock::now();
-      forward(f, ft, pos, caps, B, N, T, loss, training, es, /*defer_loss=*/true);
-      set_pending_loss(loss);
-      auto t1 = std::chrono::steady_clock::now();
-      backward(es, /*step_params=*/true);  // + bucketed RCCL all-reduce (DP) and Adam
-      if (host_timing) {
-        auto t2 = std::chrono::steady_clock::now();
-        tf += std::chrono::duration<double, std::micro>(t1 - t0).count();
-        tb += std::chrono::duration<double, std::micro>(t2 - t1).count();
-        if (++nsteps % 20 == 0) {
-          std::fprintf(stderr, "[capgen host] enqueue per step: forward %.1f us, backward %.1f us\n", tf / 20, tb / 20);
-          tf = tb = 0;
-        }
-      }
-    };
-    // under DP the forward graph holds the count and partial-CE all-reduces (RCCL ops capture);
-    // a host-set global count (capgen_dp_set_global_count) runs the forward eagerly instead --
-    // its pinned-memory copy must stay ordered against the host write
-    if (!graph_on && fwd_graph && !count_override) {
-      // forward replayed as one linear hipGraph (cheap to launch: ~0.1 us/node of host time vs
-      // ~2.7 us per eager launch, tools/kprobe.hip); backward issued eagerly on three streams
-      // (a multi-branch graph costs the same host time per node as eager issue on ROCm 7)
-      if (!(have_fwd_graph() && fkey == k)) {
+    if (fwd_graph) {
+      // forward replayed as one hipGraph (cheap to launch: ~0.1 us/node of host time vs ~2.7 us per
+      // eager launch, tools/kprobe.hip); backward issued eagerly on three streams (a multi-branch
+      // graph costs the same host time per node as eager issue on ROCm 7)
+      if (!(fexec && fkey == k)) {
         drop_graph();
-        if (!tuned(B, N, T)) {  // autotune every GEMM shape outside the capture
-          forward(f, ft, pos, caps, B, N, T, loss, /*drop_on=*/false, es);
-          backward(es);
-          hz::host_sync(es);
-          tuned_shapes.push_back({B, N, T});
-        }
-        hipGraph_t graph = nullptr;
-        // split capture needs the decoder front on its own stream
-        cap_split = fwd_split() && overlap_front && es2 != es;
-        CAPGEN_HIP(hipStreamBeginCapture(es, hipStreamCaptureModeThreadLocal));
-        try {
-          forward(f, ft, pos, caps, B, N, T, loss, training, es, /*defer_loss=*/true);
-        } catch (...) {
-          (void)hipStreamEndCapture(es, &graph);
-          if (graph) (void)hipGraphDestroy(graph);
-          cap_split = false;
-          for (auto& x : fg)
-            if (x) (void)hipGraphDestroy(x), x = nullptr;
-          throw;
-        }
-        CAPGEN_HIP(hipStreamEndCapture(es, &graph));
-        if (cap_split) {
-          fg[3] = graph;
-          for (int i = 0; i < 4; ++i) {
-            CAPGEN_HIP(hipGraphInstantiate(&fx[i], fg[i], nullptr, nullptr, 0));
-            CAPGEN_HIP(hipGraphDestroy(fg[i]));
-            fg[i] = nullptr;
-          }
-          cap_split = false;
-        } else {
-          CAPGEN_HIP(hipGraphInstantiate(&fexec, graph, nullptr, nullptr, 0));
-          CAPGEN_HIP(hipGraphDestroy(graph));
-        }
+        tune_once(f, ft, pos, caps, B, N, T, loss);
+        fexec = capture(es, eager_fwd);
         fkey = k;
       }
-      const bool host_timing = knob(Knob::HostTiming) != 0;  // (debug build)
-      static double tb = 0, tl = 0;
-      static int nsteps = 0;
-      auto t0 = std::chrono::steady_clock::now();
-      launch_fwd(es);
-      auto t1 = std::chrono::steady_clock::now();
-      fB = B, fN = N, fT = T, fwd_drop = training;  // host state forward() would have set
-      set_pending_loss(loss);
-      backward(es, /*step_params=*/true);
-      if (host_timing) {
-        auto t2 = std::chrono::steady_clock::now();
-        tl += std::chrono::duration<double, std::micro>(t1 - t0).count();
-        tb += std::chrono::duration<double, std::micro>(t2 - t1).count();
-        if (++nsteps % 20 == 0) {
-          std::fprintf(stderr, "[capgen host] per step: forward graph launch %.1f us, backward enqueue %.1f us\n",
-                       tl / 20, tb / 20);
-          tl = tb = 0;
-        }
-      }
+      halves(es, [&] { CAPGEN_HIP(hipGraphLaunch(fexec, es)); }, "forward graph launch");
     } else if (!graph_on) {
-      body();
+      halves(es, eager_fwd, "forward enqueue");
     } else {
       if (!(gexec && gkey == k)) {
         drop_graph();
-        // one eager forward+backward (no all-reduce, no Adam) so every GEMM shape of the
-        // step is autotuned outside the capture; its gradients are overwritten below
-        if (!tuned(B, N, T)) {
-          forward(f, ft, pos, caps, B, N, T, loss, /*drop_on=*/false, es);  // no RNG advance
-          backward(es);
-          hz::host_sync(es);
-          tuned_shapes.push_back({B, N, T});
-        }
-        hipGraph_t graph = nullptr;
-        CAPGEN_HIP(hipStreamBeginCapture(es, hipStreamCaptureModeThreadLocal));
-        try {
-          body();
-        } catch (...) {
-          (void)hipStreamEndCapture(es, &graph);
-          if (graph) (void)hipGraphDestroy(graph);
-          throw;
-        }
-        CAPGEN_HIP(hipStreamEndCapture(es, &graph));
-        CAPGEN_HIP(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
-        CAPGEN_HIP(hipGraphDestroy(graph));
+        tune_once(f, ft, pos, caps, B, N, T, loss);
+        gexec = capture(es, [&] { halves(es, eager_fwd, "forward enqueue"); });
         gkey = k;
       }
       // the replay runs the captured Adam and re-cast of the shadow with no host code: the weight
@@ -1772,9 +1648,10 @@ struct capgen_engine {
     ensure_acts(B, N, T);
     enter(cs);
     const int Lq = T - 1, Md = B * Lq;
-    need_logits = true;  // rl_rows samples from the logits
-    forward(f, ft, pos, caps, B, N, T, nullptr, training, es);
-    need_logits = false;
+    {
+      Scoped<bool> logits_on(need_logits, true);  // rl_rows samples from the logits
+      forward(f, ft, pos, caps, B, N, T, nullptr, training, es);
+    }
     rl_rows(a.logits, Md, L.V, a.rl_sample, a.rl_lse, a.rl_logp, a.rl_ent, es);
     rl_image(a.rl_sample, a.rl_ent, B, Lq, a.rl_ent_img, a.rl_scal, es);
     if (sample_out) rl_export(a.rl_sample, Md, sample_out, es);
@@ -1809,42 +1686,14 @@ struct capgen_engine {
   // decoding (model.py:101-200), KV-cached.  Bit-identical to recomputing the prefix: row
   // results of every kernel are independent of how many rows/positions are in the launch.
   void encode_only(const void* feats, DType ft, const float* pos, int B, int N, hipStream_t s) {
-    const int Me = B * N, d = L.d, He = L.He, dke = d / He;
+    const int Me = B * N, d = L.d;
     ensure_acts(B, N, 2);
     pack_encoder_input(feats, ft, pos, Me, L.F, L.P, L.Kp, a.Aenc, act, a.valid, s);
-    if (L.has_img) {
-      image_objects_fwd(B, N, false, s);
-    } else {
-      linear(a.Aenc, L.Kp, L.enc_emb_W, L.Kp, a.tmp, d, act, Me, d, L.Kp, nullptr, 0, s);
-      LnFwd ln;
-      ln.M = Me, ln.d = d, ln.a = a.tmp, ln.gamma = P(L.enc_lng), ln.beta = P(L.enc_lnb), ln.y = a.X[0];
-      lnf(ln, s);
-    }
-    RowMask emask{};
-    if (cfg.encode_mask) emask.valid = a.valid;
-    for (int l = 0; l < L.Le; ++l) {
-      const auto& w = L.enc[l];
-      auto& A = a.enc[l];
-      AttnGeom g;
-      g.B = B, g.H = He, g.Lq = N, g.Lk = N, g.dk = dke;
-      g.q = A.qkv, g.q_ld = 3 * d, g.q_bs = (int64_t)N * 3 * d;
-      g.k = at(A.qkv, d), g.k_ld = 3 * d, g.k_bs = (int64_t)N * 3 * d;
-      g.v = at(A.qkv, 2 * d), g.v_ld = 3 * d, g.v_bs = (int64_t)N * 3 * d;
-      g.o_ld = d, g.o_bs = (int64_t)N * d;
-      if (cfg.encode_mask) g.key_valid = a.valid, g.kv_bs = N, g.causal = 1;
-      g.temperature = std::sqrt((float)dke);
-      self_attention(a.X[l], w.Wqkv, Me, d, g, A.qkv, A.att, nullptr, s);
-      linear(A.att, d, w.Wo, d, a.tmp, d, act, Me, d, d, nullptr, 0, s);
-      LnFwd l1;
-      l1.M = Me, l1.d = d, l1.a = a.tmp, l1.res = a.X[l], l1.gamma = P(w.ln1g), l1.beta = P(w.ln1b), l1.y = A.Y;
-      lnf(l1, s);
-      linear(A.Y, d, w.W1, d, A.H, L.fe, act, Me, L.fe, d, P(w.b1), 1, s);
-      linear(A.H, L.fe, w.W2, L.fe, a.tmp, d, act, Me, d, L.fe, nullptr, 0, s);
-      LnFwd l2;
-      l2.M = Me, l2.d = d, l2.a = a.tmp, l2.a_bias = P(w.b2), l2.res = A.Y, l2.gamma = P(w.ln2g);
-      l2.beta = P(w.ln2b), l2.mask = emask, l2.y = a.X[l + 1];
-      lnf(l2, s);
-    }
+    if (L.has_img) image_objects_fwd(B, N, false, s);
+    else enc_embed_fwd(Me, /*keep=*/false, s);
+    for (int l = 0; l < L.Le; ++l)
+      enc_layer_fwd(L.enc[l], a.enc[l], a.X[l], a.X[l + 1], B, N, cfg.encode_mask ? a.valid : nullptr, l, false, s,
+                    /*keep=*/false);
     linear(a.X[L.Le], d, L.Wkv_all, d, a.KV, (int64_t)L.Ld * 2 * L.dd, act, Me, L.Ld * 2 * L.dd, d, nullptr, 0, s);
   }
 
@@ -1877,8 +1726,6 @@ struct capgen_engine {
     p.take(g.bprob2, R);
     p.take(g.bsrc, R);
     p.take(g.btok, R);
-    p.take(g.out_ids, (size_t)R * (Tc + 1));
-    p.take(g.out_attn, (size_t)(Tc - 1) * R * N);
   }
   void ensure_gen(int R, int N) {
     if (gws && R <= g.R && N <= g.N) return;
@@ -1887,7 +1734,6 @@ struct capgen_engine {
       hz::host_sync(es);
       CAPGEN_HIP(hipFree(gws));
       gws = nullptr;
-      drop_gen_graph();
     }
     Planner p;
     plan_gen(p, nR, nN);
@@ -2073,17 +1919,7 @@ struct capgen_engine {
     ensure_acts(B, N, 2);
     ensure_gen(B, N);
     ensure_dtiles();
-    const GenKey key{(attn_out ? 1 : 0) + (decode_logsm ? 8 : 0), feats, pos, (int)ft, B, N, 0};
-    gen_run(key, [&] { greedy_body(feats, ft, pos, B, N, g.out_ids, attn_out ? g.out_attn : nullptr, s); }, s);
-    CAPGEN_HIP(hipMemcpyAsync(ids_out, g.out_ids, sizeof(int64_t) * B * (L.maxlen + 1), hipMemcpyDeviceToDevice, s));
-    if (attn_out)
-      CAPGEN_HIP(hipMemcpyAsync(attn_out, g.out_attn, sizeof(float) * (L.maxlen - 1) * B * N, hipMemcpyDeviceToDevice,
-                                s));
-  }
-  void greedy_body(const void* feats, DType ft, const float* pos, int B, int N, int64_t* ids_out, float* attn_out,
-                   hipStream_t s) {
     encode_only(feats, ft, pos, B, N, s);
-    ensure_gen(B, N);
     build_dtiles(s);
     const int Tc = L.maxlen, W = L.maxlen + 1;
     init_gen_ids_kernel<<<(B * std::max(W, Tc) + 255) / 256, 256, 0, s>>>(ids_out, B, W, g.ids, Tc);
@@ -2105,14 +1941,8 @@ struct capgen_engine {
     ensure_acts(B, N, 2);
     ensure_gen(k * B, N);
     ensure_dtiles();
-    const GenKey key{2 + (decode_logsm ? 8 : 0), feats, pos, (int)ft, B, N, k};
-    gen_run(key, [&] { beam_body(feats, ft, pos, B, N, k, g.out_ids, s); }, s);
-    CAPGEN_HIP(hipMemcpyAsync(ids_out, g.out_ids, sizeof(int64_t) * B * L.maxlen, hipMemcpyDeviceToDevice, s));
-  }
-  void beam_body(const void* feats, DType ft, const float* pos, int B, int N, int k, int64_t* ids_out, hipStream_t s) {
-    const int R = k * B, Tc = L.maxlen, Tw = L.maxlen, dd = L.dd;
+    const int R = k * B, Tc = L.maxlen, Tw = L.maxlen;
     encode_only(feats, ft, pos, B, N, s);
-    ensure_gen(R, N);
     build_dtiles(s);
     init_gen_ids_kernel<<<(R * Tc + 255) / 256, 256, 0, s>>>(g.seq, R, Tw, g.ids, Tc);
     CAPGEN_HIP(hipGetLastError());
@@ -2590,15 +2420,11 @@ int capgen_train_step_indexed(capgen_t* h, const void* feat_store, int feats_dty
   return guarded([&] {
     set_device(h);
     require(n_images >= 1, "train_step_indexed: empty store");
-    h->in_idx = img_idx;
     h->in_n_img = n_images;
-    try {
+    {
+      Scoped<const int32_t*> indexed(h->in_idx, img_idx);
       h->train_step(feat_store, dt(feats_dtype), pos_store, caps, B, N, T, loss_out, (hipStream_t)stream);
-    } catch (...) {
-      h->in_idx = nullptr;
-      throw;
     }
-    h->in_idx = nullptr;
     h->dp_check((hipStream_t)stream, loss_out);
   });
 }

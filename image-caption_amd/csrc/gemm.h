@@ -52,8 +52,6 @@ struct GemmArgs {
   float2* dec_stats = nullptr;
   int64_t dec_ld = 0;
   uint64_t* stamp = nullptr;  // diagnostic timestamps (capgen_common.h StampScope); grouped: p[0]'s
-  int wt = -1;                // write-through (sc1) C stores (bf16 path): 1/0, -1 = wt_default()
-  int pad3_ = 0;
   // LayerNorm folded into the consumer (register-B path, K = 512; the decode step): the LayerNorm
   // input is v = A (+ ln_res, bf16 [M][K]), the kernel multiplies
   // y = ((v - mean) * rstd * ln_gamma + ln_beta) * keep (keep = 0 for rows m with
@@ -72,8 +70,8 @@ struct GemmArgs {
   const int32_t* a_ids = nullptr;
   int64_t a_ids_ld = 0;
 };
-// 4 ints + 37 eight-byte fields (pointers, int64s, int/float pairs): the size leaves no room for padding
-static_assert(sizeof(GemmArgs) == 16 + 37 * 8, "GemmArgs must have no padding");
+// 4 ints + 36 eight-byte fields (pointers, int64s, int/float pairs): the size leaves no room for padding
+static_assert(sizeof(GemmArgs) == 16 + 36 * 8, "GemmArgs must have no padding");
 
 // Independent GEMMs of one layout launched as ONE grid (tiles problem after problem).
 constexpr int kMaxGroup = 8;

@@ -592,12 +592,6 @@ static void gemm_grouped_impl(const GemmArgs* ps, int n, DType out, bool ta, boo
   int dev = 0;
   CAPGEN_HIP(hipGetDevice(&dev));
   require(g_zero_page[dev] != nullptr, "gemm: gemm_init() not called on this device");
-  std::vector<GemmArgs> pw(ps, ps + n);  // write-through default, as gemm_bf16
-  for (auto& g : pw) {
-    if (g.wt < 0) g.wt = wt_default();
-    if ((int64_t)g.M * g.ldc * (int64_t)dsize(out) >= (int64_t)0x7FFFFFFF) g.wt = 0;
-  }
-  ps = pw.data();
   for (int i = 0; i < n; ++i) {
     const GemmArgs& g = ps[i];
     require(g.M > 0 && g.N > 0 && g.K > 0 && g.N % 4 == 0 && g.ldc % 4 == 0 && (g.aux == nullptr || g.ldaux % 4 == 0),
@@ -729,10 +723,7 @@ void gemm_init() {
   }
 }
 
-void gemm_bf16(const GemmArgs& g_in, DType out, bool ta, bool tb, hipStream_t s) {
-  GemmArgs g = g_in;
-  if (g.wt < 0) g.wt = wt_default();
-  if ((int64_t)g.M * g.ldc * (int64_t)dsize(out) >= (int64_t)0x7FFFFFFF) g.wt = 0;  // (32-bit buffer offsets)
+void gemm_bf16(const GemmArgs& g, DType out, bool ta, bool tb, hipStream_t s) {
   int dev = 0;
   CAPGEN_HIP(hipGetDevice(&dev));
   require(g_zero_page[dev] != nullptr, "gemm: gemm_init() not called on this device");

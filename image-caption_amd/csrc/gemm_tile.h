@@ -94,9 +94,9 @@ struct Op {
   // `s_nop 4` opens the statement: hipcc pads no hazard into or out of an asm string, and the
   // descriptor / soffset SGPRs may come straight from a VALU write (v_readlane when hipcc restores
   // spilled SGPRs, v_readfirstlane) -- VALU-writes-SGPR -> VMEM-reads-it needs 5 wait states, and
-  // the M0 write just before the statement 1.  Without them the DMA read a stale descriptor: the
-  // round-4 persistent FFN's wrong W2 tiles (a kernel whose SGPR pressure made hipcc restore the W2
-  // operand's descriptor by v_readlane right before the DMA; tools/persist_ffn.py).
+  // the M0 write just before the statement 1.  Without them the DMA can read a stale descriptor
+  // (seen once, in a kernel whose SGPR pressure made hipcc restore an operand's descriptor by
+  // v_readlane right before the DMA: wrong tiles at every grid size).
   __device__ __forceinline__ void dma(uint32_t v, uint32_t soff, char* lds) const {
     asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(v), "s"(rsrc), "s"(soff),
                  "{m0}"((unsigned)(uintptr_t)lds)
@@ -503,7 +503,6 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& g, const f32x4 (&a
   TO* __restrict__ C = reinterpret_cast<TO*>(g.C);
   TO* __restrict__ C2 = reinterpret_cast<TO*>(g.C2);
   const bf16* __restrict__ aux = reinterpret_cast<const bf16*>(g.aux);
-  const __amdgpu_buffer_rsrc_t crs = wt_rsrc(g.C);
   const int fr = lane & 15, fq = lane >> 4;
   if constexpr (sizeof(TO) == 2) {
     if (g.ce_stats) {  // fused cross-entropy epilogue (GemmArgs::ce_stats)
@@ -670,19 +669,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& g, const f32x4 (&a
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] += cold[i][j][r];
       }
-      if (g.wt > 0 && !hi) {  // write-through (capgen_common.h wt_rsrc)
-        const uint32_t off = (uint32_t)(((int64_t)m * g.ldc + n) * (int64_t)sizeof(TO));
-        if constexpr (sizeof(TO) == 4) {
-          wt_store16(crs, off, wt_u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]),
-                                        __float_as_uint(v[3])});
-        } else {
-          typedef __attribute__((ext_vector_type(4))) __bf16 b4;
-          const b4 x = b4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-          wt_store8(crs, off, __builtin_bit_cast(wt_u32x2, x));
-        }
-      } else {
-        store4<TO>(cp, v);
-      }
+      store4<TO>(cp, v);
       if (g.colsum) {  // column sums of the stored values (as rounded to TO), from registers
 #pragma unroll
         for (int r = 0; r < 4; ++r) cs[r] += (float)(TO)v[r];

@@ -23,7 +23,6 @@ struct LnFwd {
   float* mean = nullptr;
   float* rstd = nullptr;
   uint64_t* stamp = nullptr;  // diagnostic timestamps (StampScope)
-  int wt = -1;                // write-through (sc1) y / v_save stores: 1/0, -1 = wt_default()
 };
 void layernorm_fwd(const LnFwd& a, DType t, hipStream_t s);
 
@@ -46,7 +45,6 @@ struct LnBwd {
   int stripes = 1;
   int64_t stripe_stride = 0;
   uint64_t* stamp = nullptr;  // diagnostic timestamps (StampScope)
-  int wt = -1;                // write-through (sc1) d_res / d_a stores: 1/0, -1 = wt_default()
 };
 void layernorm_bwd(const LnBwd& a, DType t, hipStream_t s);
 

@@ -27,7 +27,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1, help="untimed calls first (CAPGEN_GEN_GRAPH=1 captures on the 2nd)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed calls first (the first one tunes GEMM shapes and sizes the workspaces)")
     ap.add_argument("--modes", default="beam5,greedy")
     args = ap.parse_args()
     cfg = preset("C2", dtype="bf16")
