@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CAPGEN_LIB_PATH") or os.path.join(_HERE, "libcapgen.so")  # (diagnostic builds)
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 F32, BF16 = 0, 1
 
@@ -69,6 +69,8 @@ _SIGS = {
     "capgen_copy_logits": (C.c_int, [_P, _P, C.c_int64, _P]),
     "capgen_greedy": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P]),
     "capgen_beam": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "capgen_sample": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, _P, _P,
+                                _P]),
     "capgen_set_rng_seed": (C.c_int, [_P, C.c_uint64]),
     "capgen_debug_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int,
                                     _P, C.c_int64, C.c_int, C.c_int, _P, C.c_float, C.c_int, C.c_int, _P]),
@@ -114,6 +116,8 @@ _SIGS = {
     "capgen_debug_arena_checksum": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_uint64), _P]),
     "capgen_debug_argmax_softmax": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int,
                                               _P]),
+    "capgen_debug_sample_softmax": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint32, _P,
+                                              C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int, _P]),
     "capgen_debug_slab_argmax": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, _P]),
     "capgen_debug_beam_step_topk": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
                                               _P, _P]),

@@ -238,6 +238,23 @@ class Engine:
                                         _stream(self.device)))
         return ids
 
+    def sample(self, feats, pos, n_samples=1, temperature=1.0, top_k=0, seed=0, want_logp=True):
+        """n_samples captions per image drawn from softmax(logits / temperature) over the top_k largest
+        logits (0: the whole vocabulary), KV-cached, one encoder pass (capgen_sample).  Returns
+        (ids int64 [n, B, T+1] laid out as greedy's, logp f32 [n, B, T-1] or None): logp holds each
+        token's log-probability under the distribution it was drawn from.  One (seed, inputs,
+        weights) gives one result."""
+        f, ft, p, _ = self._inputs(feats, pos)
+        B, N, _ = f.shape
+        n, T = int(n_samples), self.cfg.max_length
+        rows = max(n, 0) * B
+        ids = torch.empty(rows, T + 1, dtype=torch.int64, device=self.device)
+        logp = torch.empty(rows, T - 1, dtype=torch.float32, device=self.device) if want_logp else None
+        _lib.check(self.lib.capgen_sample(self.h, _ptr(f), ft, _ptr(p), B, N, n, float(temperature), int(top_k),
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(ids), _ptr(logp),
+                                          _stream(self.device)))
+        return ids.view(n, B, T + 1), (logp.view(n, B, T - 1) if want_logp else None)
+
     # ---- SCST (SelfCriticNetwork) -------------------------------------------------------
     def rl_sample(self, feats, pos, caps):
         """Teacher-forced forward + PolicyNetwork.sample (model_RL.py:75-97): returns

@@ -14,7 +14,7 @@ import torch
 from .config import CapgenConfig
 from .model import PolicyNetwork, Transformer
 from .staging import HostBatchStager
-from .utils import decode_captions, load_word_to_idx
+from .utils import decode_captions, load_word_to_idx, sequence_logprob
 
 
 def _on_device(t) -> bool:
@@ -29,6 +29,7 @@ class MODEL_init:
             word_to_idx = load_word_to_idx(word_to_idx_path)
         self.num_vocab = len(word_to_idx)
         self.idx_to_word = {i: w for w, i in word_to_idx.items()}
+        self.end_idx = word_to_idx.get("<END>")
         self.model = None
 
     def train_step(self, *a, **k):
@@ -49,6 +50,18 @@ class MODEL_init:
             return self.decode_captions(ids.cpu().numpy()), None
         assert isinstance(beam_size, int)
         assert beam_size > 1 or beam_size in [None, 1]
+
+    def sample_captions(self, object_features, position_features, n_samples=1, temperature=1.0, top_k=0, seed=None):
+        """n_samples captions per image drawn from the model's distribution (temperature / top-k
+        sampling): (captions, logprob) -- n lists of B strings and each caption's log-probability
+        [n, B] (f32, on the model's device: the sum of its token log-probabilities through <END>)."""
+        ids, logp = self.model.sample_caption_vector(object_features=object_features,
+                                                     position_features=position_features, n_samples=n_samples,
+                                                     temperature=temperature, top_k=top_k, seed=seed)
+        host = ids.cpu().numpy()
+        end = -1 if self.end_idx is None else self.end_idx  # (no <END> in the vocabulary: every token counts)
+        logprob = sequence_logprob(ids[..., 1:logp.shape[-1] + 1], logp, end)
+        return [self.decode_captions(host[j]) for j in range(host.shape[0])], logprob
 
     def decode_captions(self, caption_vector):
         return decode_captions(caption_vector, self.idx_to_word)

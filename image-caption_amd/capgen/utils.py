@@ -29,6 +29,20 @@ def decode_captions(captions, index_to_word):
     return out
 
 
+def sequence_logprob(ids, logp, end_id):
+    """Log-probability of each sampled caption: the sum of its token log-probabilities up to and
+    including the first <END> (all of them when there is none).  ids [..., T] are the sampled tokens
+    aligned with logp [..., T] (Engine.sample's ids[..., 1:T+1] and logp); returns [...]."""
+    import torch
+
+    ids, logp = torch.as_tensor(ids), torch.as_tensor(logp)
+    if ids.shape != logp.shape:
+        raise ValueError("capgen: sequence_logprob needs ids and logp of one shape")
+    ended = (ids == end_id).to(torch.int64).cumsum(-1)
+    keep = (ended - (ids == end_id).to(torch.int64)) == 0  # no <END> strictly before this position
+    return torch.where(keep, logp, torch.zeros_like(logp)).sum(-1)
+
+
 class _VocabUnpickler(pickle.Unpickler):
     """word_index.pkl holds a plain {str: int} dict; refuse anything that is not data."""
 

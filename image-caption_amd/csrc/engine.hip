@@ -2001,6 +2001,38 @@ struct capgen_engine {
     CAPGEN_HIP(hipMemcpyAsync(ids_out, g.seq, sizeof(int64_t) * B * Tw, hipMemcpyDeviceToDevice, s));
   }
 
+  // Sampled decoding: n draws per image from softmax(logits / temperature) over the top_k logits
+  // (0: the whole vocabulary), rows j * B + b as beam's, one encoder pass, every row its own K/V
+  // cache.  Tokens are drawn to the end (<END> is not special, as in greedy); logp_out (nullable)
+  // [R, max_length - 1]: each token's log-probability under the distribution it was drawn from.
+  // The selection reads the f32 logits of either decode mode (sample_softmax, ops.hip); position t
+  // draws at site kSampleSite0 + t, above every dropout site (< 2048).
+  static constexpr uint32_t kSampleSite0 = 0x5A00;
+  void sample(const void* feats, DType ft, const float* pos, int B, int N, int n, float temperature, int top_k,
+              uint64_t sd, int64_t* ids_out, float* logp_out, hipStream_t s) {
+    require(n >= 1 && n <= 16, "sample: n_samples must be in [1, 16]");
+    require(temperature > 0.f && temperature < INFINITY, "sample: temperature must be > 0 and finite");
+    require(top_k >= 0 && top_k <= 16 && top_k <= L.V, "sample: top_k must be in [0, min(16, num_vocab)]");
+    require(B >= 1 && N >= 1 && N <= 64, "sample: need B >= 1 and N in [1, 64]");
+    require((int64_t)n * B * L.V < ((int64_t)1 << 32), "sample: n_samples * B * num_vocab must be < 2^32");
+    require(ids_out != nullptr, "sample: null ids_out");
+    const float inv_tau = 1.f / temperature;
+    require(inv_tau > 0.f && inv_tau < INFINITY, "sample: temperature out of range");
+    const int R = n * B, Tc = L.maxlen, W = L.maxlen + 1;
+    ensure_acts(B, N, 2);
+    ensure_gen(R, N);
+    ensure_dtiles();
+    encode_only(feats, ft, pos, B, N, s);
+    build_dtiles(s);
+    init_gen_ids_kernel<<<(R * std::max(W, Tc) + 255) / 256, 256, 0, s>>>(ids_out, R, W, g.ids, Tc);
+    CAPGEN_HIP(hipGetLastError());
+    for (int t = 0; t < L.maxlen - 1; ++t) {
+      dec_step(R, B, N, t, g.cache, g.ids, false, s);
+      sample_softmax(g.logits, R, L.V, inv_tau, top_k, sd, kSampleSite0 + (uint32_t)t, ids_out, W, t + 1,
+                     g.ids + t + 1, Tc, logp_out, Tc - 1, t, s);
+    }
+  }
+
   ~capgen_engine() {
     if (es) (void)hipStreamSynchronize(es);
     drop_graph();
@@ -2356,6 +2388,17 @@ int capgen_beam(capgen_t* h, const void* feats, int ft, const float* pos, int B,
     hipStream_t cs = (hipStream_t)stream;
     h->enter(cs);
     h->beam(feats, dt(ft), pos, B, N, k, ids_out, h->es);
+    h->leave(cs);
+  });
+}
+
+int capgen_sample(capgen_t* h, const void* feats, int ft, const float* pos, int B, int N, int n_samples,
+                  float temperature, int top_k, uint64_t sd, int64_t* ids_out, float* logp_out, void* stream) {
+  return guarded([&] {
+    set_device(h);
+    hipStream_t cs = (hipStream_t)stream;
+    h->enter(cs);
+    h->sample(feats, dt(ft), pos, B, N, n_samples, temperature, top_k, sd, ids_out, logp_out, h->es);
     h->leave(cs);
   });
 }
@@ -2721,6 +2764,15 @@ int capgen_debug_arena_checksum(const float* p, int64_t n, uint64_t* out, void* 
 int capgen_debug_argmax_softmax(const float* logits, int B, int V, int64_t* ids_out, int64_t ids_ld, int col,
                                 int32_t* next_ids, int64_t next_ld, int logsm, void* stream) {
   return guarded([&] { argmax_softmax(logits, B, V, ids_out, ids_ld, col, next_ids, next_ld, (hipStream_t)stream, logsm); });
+}
+
+int capgen_debug_sample_softmax(const float* logits, int R, int V, float inv_tau, int top_k, uint64_t sd, uint32_t site,
+                                int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids, int64_t next_ld,
+                                float* logp_out, int64_t logp_ld, int logp_col, void* stream) {
+  return guarded([&] {
+    sample_softmax(logits, R, V, inv_tau, top_k, sd, site, ids_out, ids_ld, col, next_ids, next_ld, logp_out, logp_ld,
+                   logp_col, (hipStream_t)stream);
+  });
 }
 
 int capgen_debug_slab_argmax(const float* logits, const void* stats, int B, int V, int64_t* ids_out, int64_t ids_ld,

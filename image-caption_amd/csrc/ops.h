@@ -104,6 +104,12 @@ uint64_t arena_checksum(const float* p, size_t n, hipStream_t s);
 // greedy: out token = argmax(softmax(logits[b])) (first index on ties)   (model.py:126-128)
 void argmax_softmax(const float* logits, int B, int V, int64_t* ids_out, int64_t ids_ld, int col,
                     int32_t* next_ids, int64_t next_ld, hipStream_t s, int logsm = 0);
+// sampled decoding: token of row r ~ softmax(logits[r] * inv_tau) restricted to the row's top_k logits
+// (top_k = 0: every column), drawn by Gumbel-max from the counter hash of (seed, site, r * V + v);
+// logp_out (optional): its log-probability under that distribution.  Definition: ops.hip.
+void sample_softmax(const float* logits, int R, int V, float inv_tau, int top_k, uint64_t seed, uint32_t site,
+                    int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids, int64_t next_ld, float* logp_out,
+                    int64_t logp_ld, int logp_col, hipStream_t s);
 // one beam-search step (model.py:183-190): rows j*B + i (j < k_in) of logits [k_in*B][V]; the
 // k best (prev[j*B+i] + softmax or log-softmax (logsm) of row j*B+i at v) per image i ->
 // out_prob/src/tok[sel*B + i]; cand_v/cand_i: k_in*B*k scratch (each row's k finalists)

@@ -1230,6 +1230,169 @@ void beam_step_topk(const float* logits, const float* prev, int k_in, int B, int
   CAPGEN_HIP(hipGetLastError());
 }
 
+// ---- sampled decoding: temperature / top-k sampling by Gumbel-max, with the log-probability ----
+// One launch per decode position, one 256-thread workgroup per row r of logits [R][V] (f32):
+// - Scaled logits.  z_v = logits[r][v] * inv_tau (f32), with inv_tau = 1 / temperature.
+// - Candidate set C.  Every v < V when top_k == 0.  Otherwise the top_k columns of the row under
+//   (logit descending, v ascending), with 1 <= top_k <= min(16, V).
+// - Noise.  h = mix32(seed, site, (uint32_t)(r * V + v)), then u = ((h >> 9) + 0.5f) * 2^-23, then
+//   g = -logf(-logf(u)).  u is exact in f32 and lies strictly inside (0, 1).  logf, not the __logf
+//   intrinsic: the winning column usually has u close to 1, where -log u is 1e-4 ... 6e-8, and the
+//   intrinsic's absolute error is of that size.  r is the row index within the launch; the launcher
+//   requires R * V < 2^32.
+// - Token.  token = argmax over v in C of (z_v + g_v), first index on ties.  With top_k == 1 this is
+//   the argmax of the logits, first index on ties.
+// - Log-probability.  logp = z_token - M - log sum_{v in C} exp(z_v - M), with M = max over C of z_v:
+//   the log-probability under the distribution actually sampled.  Exactly 0 for top_k == 1.
+// - Stores.  ids_out[r * ids_ld + col] = token (int64); next_ids[r * next_ld] = token (int32,
+//   optional); logp_out[r * logp_ld + logp_col] = logp (optional).  Nothing else is written.
+// Gumbel-max rather than an inverse-CDF scan: one pass, a result that does not depend on the
+// summation order, and an index a float64 restatement predicts exactly wherever the two best
+// perturbed scores are not within rounding of each other.  The slab statistics of the bf16 greedy /
+// beam selection are not used: their per-slab exp-sums hold at temperature 1 only.
+// NV > 0: the row (V <= 256 NV) is read once into registers, every load up front (as
+// argmax_softmax_kernel); KM > 0: the candidate set is the row's top_k <= KM, found as
+// beam_row_topk_kernel finds a row's k best (per-thread sorted lists, k wave rounds, wave 0 merges).
+__device__ __forceinline__ float gumbel_noise(uint32_t key, uint32_t idx) {
+  const uint32_t h = lowbias32(idx ^ key);  // mix32(seed, site, idx), the key hoisted
+  const float u = ((float)(h >> 9) + 0.5f) * 0x1p-23f;
+  return -logf(-logf(u));
+}
+
+template <int NV, int KM>
+__global__ void __launch_bounds__(256) sample_softmax_kernel(const float* __restrict__ logits, int V, float inv_tau,
+                                                             int top_k, uint64_t seed, uint32_t site,
+                                                             int64_t* ids_out, int64_t ids_ld, int col,
+                                                             int32_t* next_ids, int64_t next_ld, float* logp_out,
+                                                             int64_t logp_ld, int logp_col) {
+  __shared__ float sh[4];
+  __shared__ float wv[4][16];
+  __shared__ int wi[4][16];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* x = logits + (int64_t)r * V;
+  const uint32_t key = drop_key(seed, site), base = (uint32_t)r * (uint32_t)V;
+  float xr[NV > 0 ? NV : 1];
+  if constexpr (NV > 0) {
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+      const int c = tid + 256 * u;
+      xr[u] = c < V ? x[c] : -INFINITY;
+    }
+  }
+  // the winner's (perturbed score, column, bits of its z); M and the exp-sum over C
+  float best = -INFINITY, mx = -INFINITY, se = 0.f;
+  int bidx = 0x7fffffff, bz = 0;
+  bool writer = false;
+  if constexpr (KM == 0) {
+    auto visit = [&](float xv, int c) {
+      const float z = __fmul_rn(xv, inv_tau);  // (not contracted into the add: z is an f32)
+      mx = fmaxf(mx, z);
+      const float sc = z + gumbel_noise(key, base + (uint32_t)c);
+      if (sc > best) best = sc, bidx = c, bz = __float_as_int(z);
+    };
+    if constexpr (NV > 0) {
+#pragma unroll
+      for (int u = 0; u < NV; ++u)
+        if (tid + 256 * u < V) visit(xr[u], tid + 256 * u);
+    } else {
+      for (int c = tid; c < V; c += 256) visit(x[c], c);
+    }
+    mx = block_max(mx, sh);
+    if constexpr (NV > 0) {
+#pragma unroll
+      for (int u = 0; u < NV; ++u)
+        if (tid + 256 * u < V) se += expf(__fmul_rn(xr[u], inv_tau) - mx);
+    } else {
+      for (int c = tid; c < V; c += 256) se += expf(__fmul_rn(x[c], inv_tau) - mx);
+    }
+    se = block_sum(se, sh);
+    wave_best(best, bidx, bz);
+    if (lane == 0) wv[wave][0] = best, wi[wave][0] = bidx, wi[wave][1] = bz;
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < 4; ++w)
+        if (wv[w][0] > best || (wv[w][0] == best && wi[w][0] < bidx)) best = wv[w][0], bidx = wi[w][0], bz = wi[w][1];
+      writer = true;
+    }
+  } else {
+    float tv[KM];
+    int ti[KM];
+#pragma unroll
+    for (int u = 0; u < KM; ++u) tv[u] = -INFINITY, ti[u] = 0x7fffffff;
+    if constexpr (NV > 0) {
+#pragma unroll
+      for (int u = 0; u < NV; ++u)
+        if (tid + 256 * u < V) topk_insert<KM>(tv, ti, xr[u], tid + 256 * u);
+    } else {
+      for (int c = tid; c < V; c += 256) topk_insert<KM>(tv, ti, x[c], c);
+    }
+    for (int sel = 0; sel < top_k; ++sel) {  // each wave's top_k best: the winner pops its list head
+      float hv = tv[0];
+      int hi = ti[0], hpos = lane;
+      wave_best(hv, hi, hpos);
+      if (lane == 0) wv[wave][sel] = hv, wi[wave][sel] = hi;
+      if (lane == hpos) {
+#pragma unroll
+        for (int u = 0; u + 1 < KM; ++u) tv[u] = tv[u + 1], ti[u] = ti[u + 1];
+        tv[KM - 1] = -INFINITY, ti[KM - 1] = 0x7fffffff;
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {  // the row's top_k of the waves' 4 top_k: lane sel keeps candidate sel
+      const bool on = lane < 4 * top_k;
+      float v = on ? wv[lane / top_k][lane % top_k] : -INFINITY;
+      int c = on ? wi[lane / top_k][lane % top_k] : 0x7fffffff;
+      float cx = -INFINITY;
+      int cc = 0x7fffffff;
+      for (int sel = 0; sel < top_k; ++sel) {
+        float hv = v;
+        int hi = c, hpos = lane;
+        wave_best(hv, hi, hpos);
+        if (lane == sel) cx = hv, cc = hi;
+        if (lane == hpos) v = -INFINITY, c = 0x7fffffff;
+      }
+      const bool in_c = lane < top_k;
+      const float z = in_c ? __fmul_rn(cx, inv_tau) : -INFINITY;
+      mx = wave_max(z);
+      se = wave_sum(in_c ? expf(z - mx) : 0.f);
+      best = in_c ? z + gumbel_noise(key, base + (uint32_t)cc) : -INFINITY;
+      bidx = cc, bz = __float_as_int(z);
+      wave_best(best, bidx, bz);
+      writer = lane == 0;
+    }
+  }
+  if (writer) {
+    const int token = (unsigned)bidx < (unsigned)V ? bidx : 0;  // (a row of NaNs has no winner)
+    ids_out[(int64_t)r * ids_ld + col] = token;
+    if (next_ids) next_ids[(int64_t)r * next_ld] = token;
+    if (logp_out) logp_out[(int64_t)r * logp_ld + logp_col] = (__int_as_float(bz) - mx) - logf(se);
+  }
+}
+
+using SampleKernel = void (*)(const float*, int, float, int, uint64_t, uint32_t, int64_t*, int64_t, int, int32_t*,
+                              int64_t, float*, int64_t, int);
+template <int KM>
+static SampleKernel sample_softmax_form(int V) {
+  return V <= 256 * 40 ? sample_softmax_kernel<40, KM> : sample_softmax_kernel<0, KM>;
+}
+
+void sample_softmax(const float* logits, int R, int V, float inv_tau, int top_k, uint64_t seed, uint32_t site,
+                    int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids, int64_t next_ld, float* logp_out,
+                    int64_t logp_ld, int logp_col, hipStream_t s) {
+  require(R >= 1 && V >= 1 && (int64_t)R * V < ((int64_t)1 << 32), "sample_softmax: need R, V >= 1 and R * V < 2^32");
+  require(inv_tau > 0.f && inv_tau < INFINITY, "sample_softmax: temperature must be > 0 and finite");
+  require(top_k >= 0 && top_k <= 16 && top_k <= V, "sample_softmax: top_k must be in [0, min(16, num_vocab)]");
+  require(logits && ids_out && col >= 0 && logp_col >= 0, "sample_softmax: null logits / ids_out or a negative column");
+  const SampleKernel kern = top_k == 0   ? sample_softmax_form<0>(V)
+                            : top_k <= 4 ? sample_softmax_form<4>(V)
+                            : top_k == 5 ? sample_softmax_form<5>(V)
+                            : top_k <= 8 ? sample_softmax_form<8>(V)
+                                         : sample_softmax_form<16>(V);
+  kern<<<R, 256, 0, s>>>(logits, V, inv_tau, top_k, seed, site, ids_out, ids_ld, col, next_ids, next_ld, logp_out,
+                         logp_ld, logp_col);
+  CAPGEN_HIP(hipGetLastError());
+}
+
 // ---- bf16 decode selection from slab stats (GemmArgs::dec_stats) ----------------------------
 // One wave per row, 4 rows per workgroup.  The row's ceil(V/16) slab stats (8 B each, 1/8 of the
 // f32 logits) sit NS per lane in registers: one pass gives the row max M and the exp-sum

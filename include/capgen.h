@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define CAPGEN_ABI_VERSION 12
+#define CAPGEN_ABI_VERSION 13
 
 typedef struct capgen_engine capgen_t;
 
@@ -136,6 +136,19 @@ int capgen_greedy(capgen_t* h, const void* feats, int feats_dtype, const float* 
 /* Transformer.beam_search (model.py:135-200): ids_out [B, max_length] int64 device. */
 int capgen_beam(capgen_t* h, const void* feats, int feats_dtype, const float* pos, int B, int N, int beam_size,
                 int64_t* ids_out, void* stream);
+
+/* Sampled decoding: n_samples captions per image drawn from the model's distribution, one encoder
+ * pass, KV-cached.  Position t draws token ~ softmax(logits / temperature) restricted to the top_k
+ * largest logits (top_k = 0: the whole vocabulary) by Gumbel-max over the counter hash of (seed,
+ * site 0x5A00 + t, row * num_vocab + column): a (seed, inputs, weights) triple names one result.
+ * Tokens are drawn to the end (<END> is not special, as in capgen_greedy); capgen_set_decode_log_softmax
+ * has no effect.  ids_out: [n_samples * B, max_length + 1] int64 device, laid out as capgen_greedy's
+ * (<START> in column 0, last column 0), row j * B + b = sample j of image b; logp_out (nullable):
+ * [n_samples * B, max_length - 1] f32 device, each token's log-probability under the distribution it
+ * was drawn from (0 for top_k = 1).  n_samples in [1, 16], temperature > 0 and finite, top_k in
+ * [0, min(16, num_vocab)], N in [1, 64], n_samples * B * num_vocab < 2^32. */
+int capgen_sample(capgen_t* h, const void* feats, int feats_dtype, const float* pos, int B, int N, int n_samples,
+                  float temperature, int top_k, uint64_t seed, int64_t* ids_out, float* logp_out, void* stream);
 
 /* Decode scoring of capgen_greedy / capgen_beam: 0 (default) = Transformer (argmax of Softmax,
  * beams accumulate probabilities, model.py:124-128,183); 1 = PolicyNetwork, the SCST model
@@ -331,6 +344,13 @@ int capgen_debug_arena_checksum(const float* p, int64_t n, uint64_t* out, void* 
  * and K/V row table [.][Tc] from the source beams with the token at column t + 1. */
 int capgen_debug_argmax_softmax(const float* logits, int B, int V, int64_t* ids_out, int64_t ids_ld, int col,
                                 int32_t* next_ids, int64_t next_ld, int logsm, void* stream);
+/* The selection of capgen_sample, one row per workgroup (definition: csrc/ops.hip): token of row r by
+ * Gumbel-max over z = logits[r] * inv_tau on the row's top_k logits (0: all), noise from (seed, site,
+ * r * V + v) -> ids_out[r * ids_ld + col], next_ids[r * next_ld] (nullable), and its log-probability
+ * -> logp_out[r * logp_ld + logp_col] (nullable). */
+int capgen_debug_sample_softmax(const float* logits, int R, int V, float inv_tau, int top_k, uint64_t seed,
+                                uint32_t site, int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids,
+                                int64_t next_ld, float* logp_out, int64_t logp_ld, int logp_col, void* stream);
 int capgen_debug_slab_argmax(const float* logits, const void* stats, int B, int V, int64_t* ids_out, int64_t ids_ld,
                              int col, int32_t* next_ids, int64_t next_ld, void* stream);
 int capgen_debug_beam_step_topk(const float* logits, const void* stats, const float* prev, int k_in, int B, int V,

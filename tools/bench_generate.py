@@ -1,6 +1,9 @@
 """C4 (BASELINE.json configs[3]): generate() on 1 GPU — beam 5 and greedy over a batch of 256
 images (36 x 2048 region features, max_length 20), bf16, synthetic inputs, random-init C2
 weights.  KV-cached decode (model.py:101-200 restated).  Prints one JSON line per mode.
+sample1 / sample5: sampled decoding (Engine.sample, n_samples 1 / 5, top_k 0, temperature 1) -- the
+decode steps of greedy (B rows) / beam-5 (5 B rows) with one selection launch per token, so they are
+read against those two modes of the same run.
 
 Algorithmic work (KV-cached count): beam-5 1776.7 GFLOP, greedy 699.4 GFLOP per
 256-image batch.  The reference CPU path (no KV cache) took 25.0 s (beam) / 5.87 s (greedy) per
@@ -15,12 +18,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "image-caption_amd"))
 import torch  # noqa: E402
 
-from capgen import preset  # noqa: E402
+from capgen import _lib, preset  # noqa: E402
 from capgen.engine import Engine  # noqa: E402
 from capgen.params import reference_init_state_dict  # noqa: E402
 from capgen.synthetic import synthetic_batch  # noqa: E402
 
-GFLOP = {"beam5": 1776.7, "greedy": 699.4}
+GFLOP = {"beam5": 1776.7, "greedy": 699.4, "sample1": 699.4, "sample5": 1776.7}  # (sampleN: its decode steps')
 
 
 def main():
@@ -28,7 +31,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1, help="untimed calls first (the first one tunes GEMM shapes and sizes the workspaces)")
-    ap.add_argument("--modes", default="beam5,greedy")
+    ap.add_argument("--modes", default="beam5,greedy", help="of beam5, greedy, sample1, sample5")
     args = ap.parse_args()
     cfg = preset("C2", dtype="bf16")
     dev = torch.device("cuda", 0)
@@ -40,7 +43,8 @@ def main():
                               cfg.num_vocab, seed=7)
     f = f.to(dev, torch.bfloat16).contiguous()
     p = p.to(dev).contiguous()
-    runs = {"beam5": lambda: eng.beam(f, p, 5), "greedy": lambda: eng.greedy(f, p, want_attention=False)}
+    runs = {"beam5": lambda: eng.beam(f, p, 5), "greedy": lambda: eng.greedy(f, p, want_attention=False),
+            "sample1": lambda: eng.sample(f, p, n_samples=1, seed=1), "sample5": lambda: eng.sample(f, p, n_samples=5, seed=1)}
     for name, fn in runs.items():
         if name not in args.modes.split(","):
             continue
@@ -55,7 +59,7 @@ def main():
         print(json.dumps({"metric": f"generate {name} images/sec (C4: B={B}, max_length={cfg.max_length})",
                           "value": round(B / dt, 1), "unit": "images/s", "ms_per_batch": round(dt * 1e3, 3),
                           "achieved_tflops": round(GFLOP[name] * (B / 256) / dt / 1e3, 2), "dtype": "bf16",
-                          "data": "synthetic"}), flush=True)
+                          "data": "synthetic", "gemm_shapes_tuned_live": _lib.tune_live_count()}), flush=True)
 
 
 if __name__ == "__main__":
