@@ -85,6 +85,8 @@ _SIGS = {
     "capgen_debug_copy_buffer": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
     "capgen_train_step_indexed": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P,
                                             _P]),
+    "capgen_train_step_weighted": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P,
+                                             C.c_int, _P]),
     "capgen_rl_sample": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "capgen_rl_finish": (C.c_int, [_P, _P, C.c_float, _P, C.c_int, _P]),
     "capgen_debug_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
@@ -108,6 +110,10 @@ _SIGS = {
     "capgen_debug_prepare_captions": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "capgen_debug_cross_entropy_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
     "capgen_debug_ce_finish": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "capgen_debug_cross_entropy_rows_weighted": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
+                                                           C.c_int, _P]),
+    "capgen_debug_ce_finish_weighted": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                                  _P, _P]),
     "capgen_debug_loss_finalize": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P]),
     "capgen_debug_adam": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P,
                                     C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),

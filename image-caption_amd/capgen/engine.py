@@ -207,6 +207,38 @@ class Engine:
                                                       feat_store.shape[1], T, _ptr(out), _stream(self.device)))
         return out
 
+    def train_step_weighted(self, feats, pos, caps, weights, img_idx=None, train=True, out=None):
+        """Teacher-forced step on caps [B, T] whose cross entropy is weighted per caption
+        (capgen_train_step_weighted): loss = sum_b w_b sum_t [tgt != pad] CE_bt / count.  weights [B]
+        f32, any sign (the advantages of sampled roll-outs give the self-critical policy gradient).
+        img_idx [B] given: feats / pos are [n_images, N, .] and row b reads image img_idx[b], so n
+        roll-outs per image share one copy of the features; None: feats / pos are [B, N, .].
+        train=False: the weighted loss only, nothing changes.  Returns the loss tensor.  A weights
+        tensor already on the device in f32 is read in place (its pointer keys the captured graphs)."""
+        dev = self.device
+        if weights is None:
+            w = None
+        else:
+            w = torch.as_tensor(weights).to(dev, dtype=torch.float32).contiguous()
+        c = caps.to(dev, dtype=torch.int32, non_blocking=True).contiguous()
+        if c.dim() != 2 or (w is not None and w.shape != (c.shape[0],)):
+            raise ValueError("capgen: captions must be [B, T] and weights [B]")
+        B, T = c.shape
+        if img_idx is None:
+            f, ft, p, _ = self._inputs(feats, pos, c)
+            idx, n_img = None, 0
+        else:
+            f, ft, p, _ = self._inputs(feats, pos)
+            idx = img_idx.to(dev, dtype=torch.int32).contiguous()
+            if idx.shape != (B,):
+                raise ValueError("capgen: img_idx must be [B]")
+            n_img = f.shape[0]
+        out = self._loss if out is None else out
+        _lib.check(self.lib.capgen_train_step_weighted(self.h, _ptr(f), ft, _ptr(p), n_img, _ptr(idx), _ptr(c),
+                                                       _ptr(w), B, f.shape[1], T, _ptr(out), int(bool(train)),
+                                                       _stream(self.device)))
+        return out
+
     def compute_loss(self, feats, pos, caps):
         out = torch.zeros(1, dtype=torch.float32, device=self.device)
         f, ft, p, c = self._inputs(feats, pos, caps)

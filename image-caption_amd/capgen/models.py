@@ -14,7 +14,7 @@ import torch
 from .config import CapgenConfig
 from .model import PolicyNetwork, Transformer
 from .staging import HostBatchStager
-from .utils import decode_captions, load_word_to_idx, sequence_logprob
+from .utils import decode_captions, leave_one_out_baseline, load_word_to_idx, rollout_captions, sequence_logprob
 
 
 def _on_device(t) -> bool:
@@ -179,3 +179,88 @@ class SelfCriticNetwork(MODEL_init):
             out, reward = self._step(object_features, position_features, target_caption, train=False)
         return {"loss": out[0], "language_model_loss": out[1], "structure_loss": out[2],
                 "reward": torch.as_tensor(np.array(reward), dtype=torch.float32).view(-1, 1)}
+
+
+class RolloutSelfCritic(MODEL_init):
+    """Self-critical sequence training on free-running samples (Rennie et al. 2017; the n-sample
+    variant of Luo 2020) -- beside SelfCriticNetwork, the port of the reference's trainer, whose
+    "sample" is the argmax of a teacher-forced forward.
+
+    One step: engine.sample draws n_samples captions per image (one encoder pass, KV-cached); the
+    host scores them against the ground truth (CIDEr-D / BLEU-4, capgen_scst_rewards, or reward_fn);
+    the baseline is the greedy caption's reward ("greedy") or the mean of the row's other samples
+    ("mean", n_samples >= 2); one engine.train_step_weighted on the n * B sampled captions with the
+    advantages as per-caption weights ascends advantage * log p(sample).  The n * B caption rows
+    share the B images through img_idx, and the bf16 step keeps the fused classifier + CE.
+    temperature / top_k shape the behaviour policy only: the gradient is taken through the model's
+    own log-probabilities.
+
+    reward_fn(target_ids [B, L], sample_ids [B, L]) -> [B] (host numpy) replaces the scorer.
+    seed: step i draws with seed + i; None takes each step's seed from torch's CPU generator."""
+
+    def __init__(self, config: CapgenConfig | None = None, word_to_idx=None, word_to_idx_path=None,
+                 device="cuda:0", state_dict=None, n_samples=5, temperature=1.0, top_k=0, baseline="greedy",
+                 cider_reward_weight=1.0, bleu_reward_weight=0.0, df="corpus", reward_fn=None, seed=None):
+        super().__init__(word_to_idx, word_to_idx_path)
+        from .scst import RewardScorer
+        if baseline not in ("greedy", "mean"):
+            raise ValueError("capgen RolloutSelfCritic: baseline must be 'greedy' or 'mean'")
+        if baseline == "mean" and int(n_samples) < 2:
+            raise ValueError("capgen RolloutSelfCritic: baseline='mean' needs n_samples >= 2")
+        cfg = (config or CapgenConfig()).replace(num_vocab=self.num_vocab)
+        self.config = cfg
+        self.device = torch.device(device)
+        self.model = PolicyNetwork.from_config(cfg, self.device, state_dict=state_dict)
+        self.n_samples, self.temperature, self.top_k = int(n_samples), float(temperature), int(top_k)
+        self.baseline, self.reward_fn, self.seed = baseline, reward_fn, seed
+        self.steps = 0
+        self._stage = {}
+        self.scorer = None
+        if reward_fn is None:
+            self.scorer = RewardScorer(self.idx_to_word, cider_reward_weight, bleu_reward_weight, 0.0, 0.0, df=df)
+
+    _staged = TRANSFORMER._staged
+
+    def _rewards(self, target, sample):
+        fn = self.reward_fn if self.reward_fn is not None else self.scorer.scores
+        return np.asarray(fn(target, sample), dtype=np.float64).reshape(target.shape[0])
+
+    def _step(self, batch_features, batch_positions, batch_captions, train):
+        eng, n, cfg = self.model.engine, self.n_samples, self.config
+        if self.seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        else:
+            seed = int(self.seed) + self.steps
+        self.steps += int(train)  # (compute_loss draws with the next train step's seed and leaves it)
+        f, _, p, _ = eng._inputs(batch_features, batch_positions)
+        if not (_on_device(batch_features) and _on_device(batch_positions)):
+            f, p = self._staged("f", f, f.dtype), self._staged("p", p, torch.float32)
+        B = f.shape[0]
+        ids, _ = eng.sample(f, p, n, self.temperature, self.top_k, seed, want_logp=False)
+        caps = rollout_captions(ids, self.end_idx, cfg.pad_idx)  # [n, B, T]
+        target = torch.as_tensor(batch_captions)[:, 1:].cpu().numpy()
+        L = min(target.shape[1], caps.shape[-1] - 1)
+        host = caps[..., 1:].cpu().numpy()
+        r = np.stack([self._rewards(target[:, :L], host[j][:, :L]) for j in range(n)])  # [n, B]
+        if self.baseline == "greedy":
+            g = rollout_captions(eng.greedy(f, p, want_attention=False)[0], self.end_idx, cfg.pad_idx)
+            base = np.broadcast_to(self._rewards(target[:, :L], g[:, 1:].cpu().numpy()[:, :L]), r.shape)
+        else:
+            base = leave_one_out_baseline(r)
+        # persistent device buffers: the step's graphs are keyed by pointer and replay while these stay
+        adv = self._staged("w", torch.as_tensor((r - base).reshape(n * B), dtype=torch.float32), torch.float32)
+        c = self._staged("c", caps.view(n * B, -1), torch.int32)
+        idx = self._staged("i", torch.arange(B, dtype=torch.int32).repeat(n), torch.int32)
+        loss = eng.train_step_weighted(f, p, c, adv, img_idx=idx, train=train)
+        self.last_reward = r  # [n, B] sample rewards of this step (host, float64): for logging
+        return loss, r, base
+
+    def train_step(self, batch_features, batch_positions, batch_captions):
+        self._step(batch_features, batch_positions, batch_captions, train=True)
+
+    def compute_loss(self, object_features, position_features, target_caption):
+        """{'loss', 'reward' [B, 1] (mean sample reward), 'baseline_reward' [B, 1]}; nothing is updated."""
+        with torch.no_grad():
+            loss, r, base = self._step(object_features, position_features, target_caption, train=False)
+        as_col = lambda x: torch.as_tensor(np.array(x.mean(0)), dtype=torch.float32).view(-1, 1)  # noqa: E731
+        return {"loss": loss[0].clone(), "reward": as_col(r), "baseline_reward": as_col(base)}

@@ -43,6 +43,34 @@ def sequence_logprob(ids, logp, end_id):
     return torch.where(keep, logp, torch.zeros_like(logp)).sum(-1)
 
 
+def rollout_captions(ids, end_id, pad_id):
+    """Decoded ids -> teacher-forcing captions for Engine.train_step_weighted.  ids [..., max_length+1]
+    are Engine.sample's / Engine.greedy's; returns int32 [..., max_length]: <START>, the drawn tokens
+    through the first <END> inclusive, pad_id at every position strictly after it.  end_id=None cuts
+    nothing.  A drawn <NULL> (= pad_id) before <END> stays where it is: as a target it is masked like
+    any pad, as in the reference.  Pure torch: works on CPU and device tensors."""
+    import torch
+
+    ids = torch.as_tensor(ids)
+    caps = ids[..., :-1].to(torch.int32)
+    if end_id is None:
+        return caps.contiguous()
+    is_end = (caps == end_id).to(torch.int64)
+    is_end[..., 0] = 0  # position 0 is <START>, not a drawn token
+    after = (is_end.cumsum(-1) - is_end) > 0  # an <END> strictly before this position
+    return torch.where(after, torch.full_like(caps, pad_id), caps).contiguous()
+
+
+def leave_one_out_baseline(rewards):
+    """Baseline of the n-sample self-critical estimator: rewards [n, B] -> [n, B], entry (j, b) the
+    mean of the OTHER samples of row b, (sum_k r[k, b] - r[j, b]) / (n - 1).  The advantages
+    r - baseline of each row then sum to zero.  numpy, float64."""
+    r = np.asarray(rewards, dtype=np.float64)
+    if r.ndim != 2 or r.shape[0] < 2:
+        raise ValueError("capgen: the leave-one-out baseline needs rewards [n, B] with n >= 2")
+    return (r.sum(0, keepdims=True) - r) / (r.shape[0] - 1)
+
+
 class _VocabUnpickler(pickle.Unpickler):
     """word_index.pkl holds a plain {str: int} dict; refuse anything that is not data."""
 

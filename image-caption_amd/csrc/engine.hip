@@ -314,9 +314,10 @@ struct capgen_engine {
     bool drop;
     const void* idx;
     int nimg;
+    const void* w;
     bool operator==(const Key& o) const {
       return f == o.f && p == o.p && c == o.c && loss == o.loss && ft == o.ft && B == o.B && N == o.N && T == o.T &&
-             drop == o.drop && idx == o.idx && nimg == o.nimg;
+             drop == o.drop && idx == o.idx && nimg == o.nimg && w == o.w;
     }
   } gkey{}, fkey{};
   std::vector<std::array<int, 3>> tuned_shapes;
@@ -956,10 +957,10 @@ struct capgen_engine {
       if (stamp_on) ga.stamp = stamp(s, "gemm classifier+CE " + dims(Md, L.V, dd));
       gemm(ga, act, act, false, false, s);
       ce_finish(a.ce_stats, (L.V + 15) / 16, a.ce_tl, a.tgt, Md, L.V, cfg.pad_idx, a.loss_row,
-                reinterpret_cast<bf16*>(a.dlogits), s);
+                reinterpret_cast<bf16*>(a.dlogits), s, in_w, Lq);
     } else {
       linear(dec_out(), dd, L.Wc, dd, a.logits, L.V, DType::F32, Md, L.V, dd, P(L.bc), 0, s);
-      cross_entropy_rows(a.logits, a.tgt, Md, L.V, cfg.pad_idx, a.loss_row, a.dlogits, act, s);
+      cross_entropy_rows(a.logits, a.tgt, Md, L.V, cfg.pad_idx, a.loss_row, a.dlogits, act, s, in_w, Lq);
     }
     float* lo = loss_out ? loss_out : a.loss;
     last_loss = lo;
@@ -1577,7 +1578,7 @@ struct capgen_engine {
   void train_step(const void* f, DType ft, const float* pos, const int32_t* caps, int B, int N, int T, float* loss,
                   hipStream_t cs) {
     ensure_acts(B, N, T);
-    Key k{f, pos, caps, loss, (int)ft, B, N, T, training, in_idx, in_n_img};
+    Key k{f, pos, caps, loss, (int)ft, B, N, T, training, in_idx, in_n_img, in_w};
     // (the hazard checker's log runs the eager forward: the graph replays the same launches)
     // under DP the forward graph holds the count and partial-CE all-reduces (RCCL ops capture);
     // a host-set global count (capgen_dp_set_global_count) runs the forward eagerly instead --
@@ -1681,6 +1682,9 @@ struct capgen_engine {
   // resident feature store: when set, forward() gathers image in_idx[b] from feats/pos
   const int32_t* in_idx = nullptr;
   int in_n_img = 0;
+  // per-caption loss weights [B] (capgen_train_step_weighted): when set, forward()'s CE scales caption
+  // b's loss rows and logit gradients by in_w[b]; the count stays the number of non-pad targets
+  const float* in_w = nullptr;
 
   // ------------------------------------------------------------------------------------
   // decoding (model.py:101-200), KV-cached.  Bit-identical to recomputing the prefix: row
@@ -2469,6 +2473,54 @@ int capgen_train_step_indexed(capgen_t* h, const void* feat_store, int feats_dty
       h->train_step(feat_store, dt(feats_dtype), pos_store, caps, B, N, T, loss_out, (hipStream_t)stream);
     }
     h->dp_check((hipStream_t)stream, loss_out);
+  });
+}
+
+int capgen_train_step_weighted(capgen_t* h, const void* feats, int feats_dtype, const float* pos, int n_images,
+                               const int32_t* img_idx, const int32_t* caps, const float* weights, int B, int N, int T,
+                               float* loss_out, int train, void* stream) {
+  return guarded([&] {
+    set_device(h);
+    require(weights != nullptr, "train_step_weighted: weights is null");
+    require(!h->cfg.focal_loss, "train_step_weighted: focal_loss transforms an unweighted mean");
+    require(!img_idx || n_images >= 1, "train_step_weighted: empty store");
+    hipStream_t cs = (hipStream_t)stream;
+    const DType ft = dt(feats_dtype);
+    if (img_idx) h->in_n_img = n_images;
+    Scoped<const int32_t*> indexed(h->in_idx, img_idx);
+    Scoped<const float*> weighted(h->in_w, weights);
+    if (train) {
+      h->train_step(feats, ft, pos, caps, B, N, T, loss_out, cs);
+      h->dp_check(cs, loss_out);
+    } else {  // as capgen_compute_loss: the forward alone
+      h->ensure_acts(B, N, T);
+      h->enter(cs);
+      h->forward(feats, ft, pos, caps, B, N, T, loss_out, h->training, h->es);
+      h->leave(cs);
+    }
+  });
+}
+
+int capgen_debug_cross_entropy_rows_weighted(const float* logits, const int32_t* tgt, const float* row_w,
+                                             int rows_per_w, int M, int V, int pad, float* loss_row, void* dlogits,
+                                             int dtype, void* stream) {
+  return guarded([&] {
+    require(row_w != nullptr, "debug_cross_entropy_rows_weighted: row_w is null");
+    require(rows_per_w >= 1 && M % rows_per_w == 0,
+            "debug_cross_entropy_rows_weighted: rows_per_w must be >= 1 and divide M");
+    cross_entropy_rows(logits, tgt, M, V, pad, loss_row, dlogits, dt(dtype), (hipStream_t)stream, row_w, rows_per_w);
+  });
+}
+
+int capgen_debug_ce_finish_weighted(const void* stats, int64_t ld, const float* tlogit, const int32_t* tgt,
+                                    const float* row_w, int rows_per_w, int M, int V, int pad, float* loss_row,
+                                    void* dl, void* stream) {
+  return guarded([&] {
+    require(row_w != nullptr, "debug_ce_finish_weighted: row_w is null");
+    require(rows_per_w >= 1 && M % rows_per_w == 0,
+            "debug_ce_finish_weighted: rows_per_w must be >= 1 and divide M");
+    ce_finish(reinterpret_cast<const float2*>(stats), ld, tlogit, tgt, M, V, pad, loss_row,
+              reinterpret_cast<bf16*>(dl), (hipStream_t)stream, row_w, rows_per_w);
   });
 }
 

@@ -73,12 +73,14 @@ void column_sum(const void* X, int M, int N, int64_t ldx, float alpha, const flo
 void stripe_reduce(float* S, int stripes, int64_t stride, int64_t n, float* dst, int accumulate,
                    hipStream_t s, int clear = 0);
 // per-row cross entropy: loss_row[m] = lse - logit[tgt], dlogits = softmax - onehot (unscaled, 0 for pad)
+// row_w != null (both CE launchers): row m's loss and gradient are multiplied by the per-caption weight
+// row_w[m / rows_per_w] ([M / rows_per_w] f32, any sign; rows_per_w >= 1 divides M); pad rows stay 0
 void cross_entropy_rows(const float* logits, const int32_t* tgt, int M, int V, int pad, float* loss_row,
-                        void* dlogits, DType t, hipStream_t s);
+                        void* dlogits, DType t, hipStream_t s, const float* row_w = nullptr, int rows_per_w = 1);
 // fused classifier + CE, second half: dl holds exp(v - slab max) from the classifier GEMM's CE
 // epilogue (GemmArgs::ce_stats); writes loss_row and rewrites dl as softmax - onehot (0 for pad)
 void ce_finish(const float2* stats, int64_t ld, const float* tlogit, const int32_t* tgt, int M, int V, int pad,
-               float* loss_row, bf16* dl, hipStream_t s);
+               float* loss_row, bf16* dl, hipStream_t s, const float* row_w = nullptr, int rows_per_w = 1);
 // loss = sum(loss_row)/count (or FocalLoss of it); grad_scale = dloss/d(logit sums).
 // ce_in: the mean CE is given (all-reduced partials); partial: write sum(loss_row)/count only;
 // grad_scale null: the loss only (the scale was written elsewhere, e.g. by prepare_captions).

@@ -542,14 +542,19 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
   return r;
 }
 
-template <typename T>
+// WT (all three CE kernels): the row's loss and gradient are scaled by the per-caption weight
+// row_w[m / rows_per_w] (capgen_train_step_weighted); WT = false is the unweighted code, row_w unread.
+template <typename T, bool WT>
 __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logits, const int32_t* __restrict__ tgt,
-                                                 int V, int pad, float* __restrict__ loss_row, T* __restrict__ dl) {
+                                                 int V, int pad, float* __restrict__ loss_row, T* __restrict__ dl,
+                                                 const float* __restrict__ row_w, int rows_per_w) {
   __shared__ float sh[4];
   const int m = blockIdx.x;
   const float* x = logits + (int64_t)m * V;
   T* g = dl + (int64_t)m * V;
   const int y = tgt[m];
+  float w = 1.f;
+  if constexpr (WT) w = row_w[m / rows_per_w];
   if (y == pad) {
     for (int c = threadIdx.x; c < V; c += 256) g[c] = from_f<T>(0.f);
     if (threadIdx.x == 0) loss_row[m] = 0.f;
@@ -564,21 +569,29 @@ __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logit
   const float inv = 1.f / se;
   for (int c = threadIdx.x; c < V; c += 256) {
     float p = expf(x[c] - mx) * inv;
-    g[c] = from_f<T>(p - (c == y ? 1.f : 0.f));
+    float o = p - (c == y ? 1.f : 0.f);
+    if constexpr (WT) o *= w;
+    g[c] = from_f<T>(o);
   }
-  if (threadIdx.x == 0) loss_row[m] = (logf(se) + mx) - x[y];
+  if (threadIdx.x == 0) {
+    const float l = (logf(se) + mx) - x[y];
+    loss_row[m] = WT ? w * l : l;
+  }
 }
 // Register-resident variant (V % 4 == 0, V <= 1024 * NV4): the row is loaded ONCE as float4s
 // (every load in flight together: one memory round trip instead of three dependent passes),
 // max / sum-exp / gradient are computed from registers.
-template <typename T, int NV4>
+template <typename T, int NV4, bool WT>
 __global__ void __launch_bounds__(256) ce_reg_kernel(const float* __restrict__ logits, const int32_t* __restrict__ tgt,
-                                                     int V, int pad, float* __restrict__ loss_row, T* __restrict__ dl) {
+                                                     int V, int pad, float* __restrict__ loss_row, T* __restrict__ dl,
+                                                     const float* __restrict__ row_w, int rows_per_w) {
   __shared__ float sh[4];
   const int m = blockIdx.x, V4 = V >> 2;
   const float4* x = reinterpret_cast<const float4*>(logits + (int64_t)m * V);
   T* g = dl + (int64_t)m * V;
   const int y = tgt[m];
+  float w = 1.f;
+  if constexpr (WT) w = row_w[m / rows_per_w];
   if (y == pad) {
     for (int c = threadIdx.x; c < V; c += 256) g[c] = from_f<T>(0.f);
     if (threadIdx.x == 0) loss_row[m] = 0.f;
@@ -609,32 +622,51 @@ __global__ void __launch_bounds__(256) ce_reg_kernel(const float* __restrict__ l
     const int c = 4 * c4;
     float o[4] = {v[u].x * inv, v[u].y * inv, v[u].z * inv, v[u].w * inv};
     if (y >= c && y < c + 4) o[y - c] -= 1.f;
+    if constexpr (WT) o[0] *= w, o[1] *= w, o[2] *= w, o[3] *= w;
     store_f<T, 4>(g + c, o);
   }
-  if (threadIdx.x == 0) loss_row[m] = (logf(se) + mx) - logits[(int64_t)m * V + y];
-}
-
-template <typename T>
-static void ce_launch(const float* logits, const int32_t* tgt, int M, int V, int pad, float* loss_row, T* dl,
-                      hipStream_t s) {
-  if (V % 4 == 0 && V <= 1024 * 16) {
-    const int nv4 = (V / 4 + 255) / 256;
-    if (nv4 <= 4) ce_reg_kernel<T, 4><<<M, 256, 0, s>>>(logits, tgt, V, pad, loss_row, dl);
-    else if (nv4 <= 8) ce_reg_kernel<T, 8><<<M, 256, 0, s>>>(logits, tgt, V, pad, loss_row, dl);
-    else if (nv4 <= 10) ce_reg_kernel<T, 10><<<M, 256, 0, s>>>(logits, tgt, V, pad, loss_row, dl);
-    else ce_reg_kernel<T, 16><<<M, 256, 0, s>>>(logits, tgt, V, pad, loss_row, dl);
-  } else {
-    ce_kernel<T><<<M, 256, 0, s>>>(logits, tgt, V, pad, loss_row, dl);
+  if (threadIdx.x == 0) {
+    const float l = (logf(se) + mx) - logits[(int64_t)m * V + y];
+    loss_row[m] = WT ? w * l : l;
   }
 }
+
+template <typename T, bool WT>
+static void ce_launch(const float* logits, const int32_t* tgt, int M, int V, int pad, float* loss_row, T* dl,
+                      const float* row_w, int rows_per_w, hipStream_t s) {
+  if (V % 4 == 0 && V <= 1024 * 16) {
+    const int nv4 = (V / 4 + 255) / 256;
+    if (nv4 <= 4) ce_reg_kernel<T, 4, WT><<<M, 256, 0, s>>>(logits, tgt, V, pad, loss_row, dl, row_w, rows_per_w);
+    else if (nv4 <= 8) ce_reg_kernel<T, 8, WT><<<M, 256, 0, s>>>(logits, tgt, V, pad, loss_row, dl, row_w, rows_per_w);
+    else if (nv4 <= 10) ce_reg_kernel<T, 10, WT><<<M, 256, 0, s>>>(logits, tgt, V, pad, loss_row, dl, row_w, rows_per_w);
+    else ce_reg_kernel<T, 16, WT><<<M, 256, 0, s>>>(logits, tgt, V, pad, loss_row, dl, row_w, rows_per_w);
+  } else {
+    ce_kernel<T, WT><<<M, 256, 0, s>>>(logits, tgt, V, pad, loss_row, dl, row_w, rows_per_w);
+  }
+}
+// row_w != null: row m is weighted by row_w[m / rows_per_w] (M / rows_per_w weights)
+static void check_row_w(const char* who, const float* row_w, int rows_per_w, int M) {
+  if (!row_w) return;
+  require(rows_per_w >= 1 && M % rows_per_w == 0,
+          std::string(who) + ": rows_per_w must be >= 1 and divide M");
+}
 void cross_entropy_rows(const float* logits, const int32_t* tgt, int M, int V, int pad, float* loss_row, void* dl,
-                        DType t, hipStream_t s) {
+                        DType t, hipStream_t s, const float* row_w, int rows_per_w) {
   if (M <= 0) return;
-  if (hz::active())
-    hz::op(s, "cross_entropy", {hz::rd(logits, (int64_t)M * V * 4), hz::rd(tgt, (int64_t)M * 4),
-                                hz::wr(loss_row, (int64_t)M * 4), hz::wr(dl, (int64_t)M * V * dsize(t))});
-  if (t == DType::F32) ce_launch<float>(logits, tgt, M, V, pad, loss_row, (float*)dl, s);
-  else ce_launch<bf16>(logits, tgt, M, V, pad, loss_row, (bf16*)dl, s);
+  check_row_w("cross_entropy_rows", row_w, rows_per_w, M);
+  if (hz::active()) {
+    std::vector<hz::Rgn> r = {hz::rd(logits, (int64_t)M * V * 4), hz::rd(tgt, (int64_t)M * 4),
+                                hz::wr(loss_row, (int64_t)M * 4), hz::wr(dl, (int64_t)M * V * dsize(t))};
+    if (row_w) r.push_back(hz::rd(row_w, (int64_t)(M / rows_per_w) * 4));
+    hz::op(s, "cross_entropy", r.data(), r.size());
+  }
+  if (t == DType::F32) {
+    if (row_w) ce_launch<float, true>(logits, tgt, M, V, pad, loss_row, (float*)dl, row_w, rows_per_w, s);
+    else ce_launch<float, false>(logits, tgt, M, V, pad, loss_row, (float*)dl, nullptr, 1, s);
+  } else {
+    if (row_w) ce_launch<bf16, true>(logits, tgt, M, V, pad, loss_row, (bf16*)dl, row_w, rows_per_w, s);
+    else ce_launch<bf16, false>(logits, tgt, M, V, pad, loss_row, (bf16*)dl, nullptr, 1, s);
+  }
   CAPGEN_HIP(hipGetLastError());
 }
 
@@ -643,21 +675,25 @@ void cross_entropy_rows(const float* logits, const int32_t* tgt, int M, int V, i
 // workgroup per row: lse = M + log sum_c s_c exp(mx_c - M), loss_row = lse - v[tgt], and the
 // row is rewritten in place as softmax - onehot = e * exp(mx_c - lse) - onehot.  Every load of the
 // row (stats + the thread's slabs) is issued up front: one memory round trip.
-template <int SPT, int VW>
+template <int SPT, int VW, bool WT>
 __global__ void __launch_bounds__(256) ce_finish_kernel(const float2* __restrict__ stats, int64_t ld,
                                                         const float* __restrict__ tlogit,
                                                         const int32_t* __restrict__ tgt, int V, int pad,
-                                                        float* __restrict__ loss_row, bf16* __restrict__ dl) {
+                                                        float* __restrict__ loss_row, bf16* __restrict__ dl,
+                                                        const float* __restrict__ row_w, int rows_per_w) {
   // VW = elements per access: 8 (16-B loads / stores, rows 16-B aligned: V % 8 == 0) or 4
   __shared__ float sh[4];
   typedef __attribute__((ext_vector_type(VW))) __bf16 bv;
   constexpr int NQ = 16 / VW;  // accesses per 16-column slab
   const int m = blockIdx.x, nsl = (V + 15) / 16;
   bf16* row = dl + (int64_t)m * V;
-  // every load first -- target, target logit, slab stats, the row's e values -- from clamped in-range
-  // addresses with no branch around them (a load in a branch is waited for at its join): one round trip
+  // every load first -- target, target logit, caption weight, slab stats, the row's e values -- from
+  // clamped in-range addresses with no branch around them (a load in a branch is waited for at its join):
+  // one round trip
   const int y = tgt[m];
   const float tl = tlogit[m];
+  float w = 1.f;
+  if constexpr (WT) w = row_w[m / rows_per_w];
   float2 st[SPT];
   bv e[SPT][NQ];
 #pragma unroll
@@ -698,29 +734,38 @@ __global__ void __launch_bounds__(256) ce_finish_kernel(const float2* __restrict
       for (int i = 0; i < VW; ++i) {
         float x = (float)e[u][q][i] * f;
         if (y == col + i) x -= 1.f;
+        if constexpr (WT) x *= w;
         o[i] = (bf16)x;
       }
       *reinterpret_cast<bv*>(row + col) = o;
     }
   }
-  if (threadIdx.x == 0) loss_row[m] = lse - tl;
+  if (threadIdx.x == 0) loss_row[m] = WT ? w * (lse - tl) : lse - tl;
 }
 void ce_finish(const float2* stats, int64_t ld, const float* tlogit, const int32_t* tgt, int M, int V, int pad,
-               float* loss_row, bf16* dl, hipStream_t s) {
+               float* loss_row, bf16* dl, hipStream_t s, const float* row_w, int rows_per_w) {
   if (M <= 0) return;
   require(V % 4 == 0 && ld >= (V + 15) / 16, "ce_finish: V must be a multiple of 4");
+  check_row_w("ce_finish", row_w, rows_per_w, M);
   if (hz::active()) {
     using namespace hz;
-    op(s, "ce_finish", {blk(stats, M, (int64_t)((V + 15) / 16) * 8, ld * 8, RD), rd(tlogit, (int64_t)M * 4),
-                        rd(tgt, (int64_t)M * 4), wr(loss_row, (int64_t)M * 4), wr(dl, (int64_t)M * V * 2)});
+    std::vector<Rgn> r = {blk(stats, M, (int64_t)((V + 15) / 16) * 8, ld * 8, RD), rd(tlogit, (int64_t)M * 4),
+                            rd(tgt, (int64_t)M * 4), wr(loss_row, (int64_t)M * 4), wr(dl, (int64_t)M * V * 2)};
+    if (row_w) r.push_back(rd(row_w, (int64_t)(M / rows_per_w) * 4));
+    op(s, "ce_finish", r.data(), r.size());
   }
   const int spt = ((V + 15) / 16 + 255) / 256;
   // 16-B accesses when every row starts 16-B aligned (Knob::CeVec8 = 0: the 8-B form, bit-identity test)
   const bool v8 = knob(Knob::CeVec8) != 0 && V % 8 == 0 && ((uintptr_t)dl & 15) == 0;
   auto go = [&](auto spt_c) {
     constexpr int S = decltype(spt_c)::value;
-    if (v8) ce_finish_kernel<S, 8><<<M, 256, 0, s>>>(stats, ld, tlogit, tgt, V, pad, loss_row, dl);
-    else ce_finish_kernel<S, 4><<<M, 256, 0, s>>>(stats, ld, tlogit, tgt, V, pad, loss_row, dl);
+    if (row_w) {
+      if (v8) ce_finish_kernel<S, 8, true><<<M, 256, 0, s>>>(stats, ld, tlogit, tgt, V, pad, loss_row, dl, row_w, rows_per_w);
+      else ce_finish_kernel<S, 4, true><<<M, 256, 0, s>>>(stats, ld, tlogit, tgt, V, pad, loss_row, dl, row_w, rows_per_w);
+    } else {
+      if (v8) ce_finish_kernel<S, 8, false><<<M, 256, 0, s>>>(stats, ld, tlogit, tgt, V, pad, loss_row, dl, nullptr, 1);
+      else ce_finish_kernel<S, 4, false><<<M, 256, 0, s>>>(stats, ld, tlogit, tgt, V, pad, loss_row, dl, nullptr, 1);
+    }
   };
   if (spt <= 1) go(std::integral_constant<int, 1>{});
   else if (spt <= 2) go(std::integral_constant<int, 2>{});

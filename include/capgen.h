@@ -212,6 +212,26 @@ int capgen_train_step_indexed(capgen_t* h, const void* feat_store, int feats_dty
                               int n_images, const int32_t* img_idx, const int32_t* caps, int B, int N, int T,
                               float* loss_out, void* stream);
 
+/* Teacher-forced step whose cross entropy is weighted per caption:
+ *   loss = sum_b w_b sum_t [tgt_bt != pad] (lse_bt - logit_bt[tgt_bt]) / count,
+ * count = the number of non-pad targets (the global number under data parallel), exactly as in
+ * capgen_train_step.  With w_b = the advantage of a sampled caption this is the self-critical policy
+ * gradient loss over roll-outs (capgen_sample / capgen_greedy ids, scored by capgen_scst_rewards); other
+ * weights give example weighting.  weights: [B] f32 on the device, one per caption row, any sign, required;
+ * the weight enters the two row-wise CE kernels, so the bf16 step keeps the fused classifier + CE (no
+ * logits are written).  img_idx non-null: feats / pos are [n_images, N, .] stores and row b reads image
+ * img_idx[b] (capgen_train_step_indexed: n B roll-outs share B images without a copy); img_idx null:
+ * feats / pos are [B, N, .] and n_images is ignored.  train != 0: forward, backward and Adam, through every
+ * route of capgen_train_step (forward graph, capgen_set_graph, data parallel -- the same RCCL call
+ * sequence); the weights pointer is part of the graph key: a new pointer re-captures, new values behind
+ * the same pointer are read by the replay.  train == 0: the weighted loss only (no gradient, parameter or
+ * Adam-state change; dropout follows capgen_set_training).  Fails when the config has focal_loss (it
+ * transforms an unweighted mean) or weights is null.
+ * Added without a change of CAPGEN_ABI_VERSION: no existing entry changed (backward compatible). */
+int capgen_train_step_weighted(capgen_t* h, const void* feats, int feats_dtype, const float* pos, int n_images,
+                               const int32_t* img_idx, const int32_t* caps, const float* weights, int B, int N,
+                               int T, float* loss_out, int train, void* stream);
+
 /* Self-critical sequence training (SelfCriticNetwork, models.py:137-211), in two calls with the
  * host scoring the samples in between (CIDEr-D / BLEU, capgen/scst.py):
  *  capgen_rl_sample  replaces PolicyNetwork.forward + .sample (model_RL.py:75-97) and the entropy
@@ -321,6 +341,15 @@ int capgen_debug_cross_entropy_rows(const float* logits, const int32_t* tgt, int
                                     void* dlogits, int dtype, void* stream);
 int capgen_debug_ce_finish(const void* stats, int64_t ld, const float* tlogit, const int32_t* tgt, int M, int V,
                            int pad, float* loss_row, void* dl, void* stream);
+/* The same two with a per-caption weight: row m uses w = row_w[m / rows_per_w] ([M / rows_per_w] f32),
+ * loss_row[m] = w (lse - logit[tgt]), dlogits = w (softmax - onehot) rounded once to dtype; pad rows stay 0.
+ * Fail when row_w is null, rows_per_w < 1 or M % rows_per_w != 0. */
+int capgen_debug_cross_entropy_rows_weighted(const float* logits, const int32_t* tgt, const float* row_w,
+                                             int rows_per_w, int M, int V, int pad, float* loss_row, void* dlogits,
+                                             int dtype, void* stream);
+int capgen_debug_ce_finish_weighted(const void* stats, int64_t ld, const float* tlogit, const int32_t* tgt,
+                                    const float* row_w, int rows_per_w, int M, int V, int pad, float* loss_row,
+                                    void* dl, void* stream);
 int capgen_debug_loss_finalize(const float* loss_row, int M, const float* count, int focal, float* loss_out,
                                float* grad_scale, const float* ce_in, int partial, void* stream);
 /* One torch.optim.Adam step of a flat f32 arena (n % 4 == 0): adam_prepare (++*step, device int64; scal =

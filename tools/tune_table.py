@@ -7,6 +7,10 @@ shape is tuned once on an idle device (gemm_bf16.hip launch_bf16_tiles), then sa
 Afterwards every process loads the table at its first GEMM and tunes nothing live.
 
   CAPGEN_TUNE_TABLE=0 python tools/tune_table.py [--out PATH]
+
+--add-rollouts: keep the committed table (it is loaded, its rows are written back unchanged) and add
+only the shapes of the roll-out self-critical step (tools/bench_scst.py --rollouts: 5 x 64 caption rows
+over 64 images, the 320-row sampled decode) that it does not hold yet.
 """
 import argparse
 import os
@@ -15,7 +19,9 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "image-caption_amd"))
 sys.path.insert(0, os.path.join(REPO, "tests"))
-os.environ.setdefault("CAPGEN_TUNE_TABLE", "0")  # start from nothing
+ADD_ROLLOUTS = "--add-rollouts" in sys.argv[1:]
+if not ADD_ROLLOUTS:
+    os.environ.setdefault("CAPGEN_TUNE_TABLE", "0")  # start from nothing
 import torch  # noqa: E402
 
 from capgen import _lib, preset  # noqa: E402
@@ -32,8 +38,27 @@ def dev_batch(cfg, B, N, T, seed, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=_lib.TUNE_TABLE)
+    ap.add_argument("--add-rollouts", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if args.add_rollouts:
+        cfg = preset("C2", dtype="bf16", dropout=0.3)
+        eng = Engine(cfg, dev)
+        eng.load_state_dict({k: torch.from_numpy(v) for k, v in reference_init_state_dict(cfg, seed=0).items()})
+        n, B = 5, 64
+        f, p, _ = dev_batch(cfg, B, 36, cfg.max_length, 1000, dev)
+        ids, _ = eng.sample(f, p, n, 1.0, 0, 0, want_logp=False)
+        eng.greedy(f, p, want_attention=False)
+        caps = ids.view(n * B, -1)[:, :-1].to(torch.int32).contiguous()
+        idx = torch.arange(B, dtype=torch.int32, device=dev).repeat(n)
+        w = torch.linspace(-1, 1, n * B, device=dev)
+        for _ in range(2):
+            eng.train_step_weighted(f, p, caps, w, img_idx=idx)
+        eng.train_step_weighted(f, p, caps, w, img_idx=idx, train=False)
+        torch.cuda.synchronize()
+        print(f"roll-out shapes: {_lib.tune_live_count()} tuned", flush=True)
+        print(f"wrote {_lib.tune_save(args.out)} entries to {args.out}", flush=True)
+        return
     # C2 / C3 / C5 model: train step, SCST, decode
     cfg = preset("C2", dtype="bf16", dropout=0.3)
     eng = Engine(cfg, dev)
