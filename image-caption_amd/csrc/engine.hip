@@ -69,6 +69,41 @@ struct Scoped {
   ~Scoped() { ref = old; }
 };
 
+// the dense attention layout: a batch is rows x leading dimension apart, temperature sqrt(dk)
+inline AttnGeom attn_dense(int B, int H, int Lq, int Lk, int dk, const void* q, int64_t q_ld, const void* k,
+                           int64_t k_ld, const void* v, int64_t v_ld, int64_t o_ld) {
+  AttnGeom g;
+  g.B = B, g.H = H, g.Lq = Lq, g.Lk = Lk, g.dk = dk;
+  g.q = q, g.q_ld = q_ld, g.q_bs = Lq * q_ld;
+  g.k = k, g.k_ld = k_ld, g.k_bs = Lk * k_ld;
+  g.v = v, g.v_ld = v_ld, g.v_bs = Lk * v_ld;
+  g.o_ld = o_ld, g.o_bs = Lq * o_ld;
+  g.temperature = std::sqrt((float)dk);
+  return g;
+}
+
+// What the forward and the backward of one LayerNorm site share: the saved input and statistics,
+// the arena offsets of gamma, beta and the producing Linear's bias (-1: none), the row mask and
+// the dropout on the Linear's output.  ln_fwd / ln_bwd turn it into the launch descriptors.
+struct LnSite {
+  int M, d;
+  void* v;
+  float *mean, *rstd;
+  int64_t g, b, bias;
+  RowMask mask;
+  Drop drop;
+};
+
+// the step inputs that reach forward() beside its arguments (set for the scope of one C-ABI call)
+struct StepIn {
+  const int32_t* idx = nullptr;  // resident feature store: forward() gathers image idx[b] from feats/pos
+  int n_img = 0;                 // ... of n_img images
+  // per-caption loss weights [B] (capgen_train_step_weighted): forward()'s CE scales caption b's loss
+  // rows and logit gradients by w[b]; the count stays the number of non-pad targets
+  const float* w = nullptr;
+  bool operator==(const StepIn& o) const { return idx == o.idx && n_img == o.n_img && w == o.w; }
+};
+
 struct EncAct {
   void *qkv, *att, *v1, *Y, *H, *v2;
   float *P, *m1, *r1, *m2, *r2;
@@ -312,14 +347,13 @@ struct capgen_engine {
     float* loss;
     int ft, B, N, T;
     bool drop;
-    const void* idx;
-    int nimg;
-    const void* w;
+    StepIn in;
     bool operator==(const Key& o) const {
       return f == o.f && p == o.p && c == o.c && loss == o.loss && ft == o.ft && B == o.B && N == o.N && T == o.T &&
-             drop == o.drop && idx == o.idx && nimg == o.nimg && w == o.w;
+             drop == o.drop && in == o.in;
     }
   } gkey{}, fkey{};
+  StepIn in;
   std::vector<std::array<int, 3>> tuned_shapes;
   bool tuned(int B, int N, int T) const {
     for (auto& t : tuned_shapes)
@@ -361,7 +395,6 @@ struct capgen_engine {
   const float* P(int64_t off) const { return params + off; }
   float* G(int64_t off) const { return grads + off; }
   float* GS(int64_t off) const { return gstripe + (off - L.enc_lng); }  // striped small-gradient slot
-  void striped(LnBwd& lb) const { lb.stripes = NSTRIPE, lb.stripe_stride = n_small; }
   size_t es_() const { return dsize(act); }
   void* at(void* base, int64_t elems) const { return (char*)base + elems * es_(); }
 
@@ -376,7 +409,114 @@ struct capgen_engine {
   }
   // the f32 VALU attention backward reads the saved probabilities; the bf16 MFMA one recomputes
   bool keep_probs(const AttnGeom& g) const { return !(act == DType::BF16 && attention_mfma_ok(g)); }
-  static uint32_t site(int dec, int layer, int kind) { return (uint32_t)((dec * 64 + layer) * 16 + kind); }
+  // a dropout site = (encoder 0 / decoder 1, layer, kind): the hash input that makes its mask.  The
+  // values are part of the results (golden fixtures, bit-identity tests): never renumber
+  enum DropKind {
+    kDropEncAttn = 0, kDropEncMha = 1, kDropEncFfn = 2,
+    kDropDecSelfAttn = 3, kDropDecSelf = 4, kDropDecCrossAttn = 5, kDropDecCross = 6, kDropDecFfn = 7,
+    kDropMoveFirst = 0,  // (decoder, kMfLayer)
+  };
+  static constexpr int kImgLayer = 63;  // dropout-site layer index of encoder.image_encoder
+  static constexpr int kMfLayer = 62;   // dropout-site layer index of the decoder's move-first FFN
+  static uint32_t site(int dec, int layer, DropKind kind) { return (uint32_t)((dec * 64 + layer) * 16 + kind); }
+
+  // ---- the attention sites: the complete geometry (masks and dropout included) of each, built
+  // here for the forward and the backward alike (the bf16 MFMA backward recomputes the probabilities)
+  // encoder self-attention of B sequences of N rows (the image block: B = Me pairs of N = 2)
+  AttnGeom enc_self_geom(const EncAct& A, int B, int N, const uint8_t* valid, int layer, bool on) const {
+    const int d = L.d;
+    AttnGeom g = attn_dense(B, L.He, N, N, d / L.He, A.qkv, 3 * d, at(A.qkv, d), 3 * d, at(A.qkv, 2 * d), 3 * d, d);
+    if (valid) g.key_valid = valid, g.kv_bs = N, g.causal = 1;
+    g.drop = mk_drop(cfg.attention_dropout, site(0, layer, kDropEncAttn), on);
+    return g;
+  }
+  // decoder self-attention: key-pad(ids) OR causal (model.py:421-430)
+  AttnGeom dec_self_geom(int l, int B, int Lq, bool on) const {
+    const int dd = L.dd;
+    void* qkv = a.dec[l].qkv;
+    AttnGeom g = attn_dense(B, L.Hd, Lq, Lq, dd / L.Hd, qkv, 3 * dd, at(qkv, dd), 3 * dd, at(qkv, 2 * dd), 3 * dd, dd);
+    g.key_ids = a.ids, g.kid_bs = Lq, g.pad_idx = cfg.pad_idx, g.causal = 1;
+    g.drop = mk_drop(cfg.attention_dropout, site(1, l, kDropDecSelfAttn), on);
+    return g;
+  }
+  // the K/V half of decoder block l's cross-attention: its columns of a.KV (every block's K | V side
+  // by side per encoder row), N regions per image, context mask = region key-pad (model.py:82).
+  // The caller sets B, Lq and the q / o layouts.
+  AttnGeom cross_kv(int l, int N) const {
+    const int dd = L.dd;
+    const int64_t kvld = (int64_t)L.Ld * 2 * dd;
+    AttnGeom c = attn_dense(0, L.Hd, 0, N, dd / L.Hd, nullptr, 0, at(a.KV, (int64_t)l * 2 * dd), kvld,
+                            at(a.KV, (int64_t)l * 2 * dd + dd), kvld, 0);
+    c.key_valid = a.valid, c.kv_bs = N;
+    return c;
+  }
+  // decoder cross-attention at the training shape
+  AttnGeom dec_cross_geom(int l, int B, int Lq, int N, bool on) const {
+    const int dd = L.dd;
+    AttnGeom c = cross_kv(l, N);
+    c.B = B, c.Lq = Lq;
+    c.q = a.dec[l].qc, c.q_ld = dd, c.q_bs = (int64_t)Lq * dd;
+    c.o_ld = dd, c.o_bs = (int64_t)Lq * dd;
+    c.drop = mk_drop(cfg.attention_dropout, site(1, l, kDropDecCrossAttn), on);
+    return c;
+  }
+
+  // ---- the LayerNorm sites (model.py:86-90, 114-120), each described once for both directions
+  LnSite enc_embed_site(int Me) const {  // the shared norm after the region embedding (model.py:294)
+    return {Me, L.d, a.ev0, a.em0, a.er0, L.enc_lng, L.enc_lnb, -1, RowMask{}, Drop{}};
+  }
+  LnSite img_norm2_site(int Me) const {  // the shared norm again, after the image block
+    return {Me, L.d, a.siV, a.siM, a.siR, L.enc_lng, L.enc_lnb, -1, RowMask{}, Drop{}};
+  }
+  LnSite enc_ln1_site(const EncLayerOff& w, const EncAct& A, int Me, int layer, bool on) const {
+    return {Me, L.d, A.v1, A.m1, A.r1, w.ln1g, w.ln1b, -1, RowMask{}, mk_drop(cfg.dropout, site(0, layer, kDropEncMha), on)};
+  }
+  LnSite enc_ln2_site(const EncLayerOff& w, const EncAct& A, int Me, const uint8_t* valid, int layer, bool on) const {
+    RowMask mask{};
+    mask.valid = valid;
+    return {Me, L.d, A.v2, A.m2, A.r2, w.ln2g, w.ln2b, w.b2, mask, mk_drop(cfg.dropout, site(0, layer, kDropEncFfn), on)};
+  }
+  LnSite dec_embed_site(int Md) const {  // LN(E.Wel^T + PE) (model.py:432-436): no residual, no dropout
+    return {Md, L.dd, a.dv0, a.dm0, a.dr0, L.dec_lng, L.dec_lnb, -1, RowMask{}, Drop{}};
+  }
+  LnSite dec_self_site(int l, int Md, bool on) const {
+    const auto& A = a.dec[l];
+    const auto& w = L.dec[l];
+    return {Md, L.dd, A.vs, A.ms, A.rs, w.lsg, w.lsb, -1, RowMask{}, mk_drop(cfg.dropout, site(1, l, kDropDecSelf), on)};
+  }
+  LnSite dec_cross_site(int l, int Md, bool on) const {
+    const auto& A = a.dec[l];
+    const auto& w = L.dec[l];
+    return {Md, L.dd, A.vc, A.mc, A.rc, w.lcg, w.lcb, -1, RowMask{}, mk_drop(cfg.dropout, site(1, l, kDropDecCross), on)};
+  }
+  LnSite dec_ffn_site(int l, int Md, bool on) const {  // x non_pad (modules.py:201-204)
+    const auto& A = a.dec[l];
+    const auto& w = L.dec[l];
+    RowMask mask{};
+    mask.ids = a.ids, mask.pad_idx = cfg.pad_idx;
+    return {Md, L.dd, A.vf, A.mf, A.rf, w.lfg, w.lfb, w.b2, mask, mk_drop(cfg.dropout, site(1, l, kDropDecFfn), on)};
+  }
+  LnSite move_first_site(int M, bool on) const {
+    return {M, L.dd, a.mfV, a.mfM, a.mfR, L.mf_lng, L.mf_lnb, L.mf_b2, RowMask{},
+            mk_drop(cfg.dropout, site(1, kMfLayer, kDropMoveFirst), on)};
+  }
+  // y = LayerNorm(drop(a + bias) + res); keep = false (decoding): nothing is saved for a backward
+  LnFwd ln_fwd(const LnSite& s, const void* a_in, const void* res, void* y, bool keep = true) const {
+    LnFwd f;
+    f.M = s.M, f.d = s.d, f.a = a_in, f.a_bias = s.bias >= 0 ? P(s.bias) : nullptr, f.drop = s.drop, f.res = res;
+    f.gamma = P(s.g), f.beta = P(s.b), f.mask = s.mask, f.y = y;
+    if (keep) f.v_save = s.v, f.mean = s.mean, f.rstd = s.rstd;
+    return f;
+  }
+  // its backward (striped accumulators): d_res = grad wrt the residual, d_a = grad wrt a
+  LnBwd ln_bwd(const LnSite& s, const void* dy, void* d_res, void* d_a) const {
+    LnBwd lb;
+    lb.M = s.M, lb.d = s.d, lb.dy = dy, lb.v = s.v, lb.mean = s.mean, lb.rstd = s.rstd, lb.gamma = P(s.g);
+    lb.mask = s.mask, lb.drop = s.drop, lb.d_res = d_res, lb.d_a = d_a;
+    lb.dgamma = GS(s.g), lb.dbeta = GS(s.b), lb.dbias = s.bias >= 0 ? GS(s.bias) : nullptr;
+    lb.stripes = NSTRIPE, lb.stripe_stride = n_small;
+    return lb;
+  }
 
   // issue priority of a launch: kernels on the critical stream run their waves at s_setprio 3 so
   // that the weight-gradient / Adam waves of the side streams sharing their CUs yield the issue
@@ -504,17 +644,6 @@ struct capgen_engine {
     linear(X, ldx, woff, ldw, const_cast<void*>(ln.a), N, act, M, N, K, nullptr, 0, s);
     lnf(ln, s);
   }
-  // a LayerNorm backward descriptor (striped accumulators); b_off < 0: no producing-Linear bias
-  LnBwd lnb_desc(int M, int d, const void* dy, const void* v, const float* mean, const float* rstd, int64_t lng,
-                 int64_t lnb, int64_t b_off, RowMask mask, Drop drop, void* d_res, void* d_a) const {
-    LnBwd lb;
-    lb.M = M, lb.d = d, lb.dy = dy, lb.v = v, lb.mean = mean, lb.rstd = rstd, lb.gamma = P(lng), lb.mask = mask;
-    lb.drop = drop, lb.d_res = d_res, lb.d_a = d_a, lb.dgamma = GS(lng), lb.dbeta = GS(lnb);
-    lb.dbias = b_off >= 0 ? GS(b_off) : nullptr;
-    striped(lb);
-    return lb;
-  }
-
   // dX[M,K] (+)= alpha * dY[M,N] . W[N,K]
   void linear_dx(const void* dY, int64_t ldy, int64_t woff, int64_t ldw, void* dX, int64_t ldx, int M, int N, int K,
                  int beta, const void* relu_aux, const float* alpha_ptr, hipStream_t s, float* colsum = nullptr) {
@@ -752,73 +881,42 @@ struct capgen_engine {
   // attention probabilities); the launches are the same
   void enc_layer_fwd(const EncLayerOff& w, EncAct& A, const void* X, void* Xout, int B, int N, const uint8_t* valid,
                      int layer, bool drop_on, hipStream_t s, bool keep = true) {
-    const int Me = B * N, d = L.d, He = L.He, dke = d / He;
-    const float p = cfg.dropout, pa = cfg.attention_dropout;
-    AttnGeom g;
-    g.B = B, g.H = He, g.Lq = N, g.Lk = N, g.dk = dke;
-    g.q = A.qkv, g.q_ld = 3 * d, g.q_bs = (int64_t)N * 3 * d;
-    g.k = at(A.qkv, d), g.k_ld = 3 * d, g.k_bs = (int64_t)N * 3 * d;
-    g.v = at(A.qkv, 2 * d), g.v_ld = 3 * d, g.v_bs = (int64_t)N * 3 * d;
-    g.o_ld = d, g.o_bs = (int64_t)N * d;
-    if (valid) g.key_valid = valid, g.kv_bs = N, g.causal = 1;
-    g.temperature = std::sqrt((float)dke);
-    g.drop = mk_drop(pa, site(0, layer, 0), drop_on);
+    const int Me = B * N, d = L.d;
+    const AttnGeom g = enc_self_geom(A, B, N, valid, layer, drop_on);
     self_attention(X, w.Wqkv, Me, d, g, A.qkv, A.att, keep && keep_probs(g) ? A.P : nullptr, s);
-    LnFwd l1;
-    l1.M = Me, l1.d = d, l1.a = a.tmp, l1.drop = mk_drop(p, site(0, layer, 1), drop_on), l1.res = X;
-    l1.gamma = P(w.ln1g), l1.beta = P(w.ln1b), l1.y = A.Y;
-    if (keep) l1.v_save = A.v1, l1.mean = A.m1, l1.rstd = A.r1;
-    linear_ln(A.att, d, w.Wo, d, Me, d, d, l1, s);
+    linear_ln(A.att, d, w.Wo, d, Me, d, d, ln_fwd(enc_ln1_site(w, A, Me, layer, drop_on), a.tmp, X, A.Y, keep), s);
     linear(A.Y, d, w.W1, d, A.H, L.fe, act, Me, L.fe, d, P(w.b1), 1, s);
-    LnFwd l2;
-    l2.M = Me, l2.d = d, l2.a = a.tmp, l2.a_bias = P(w.b2), l2.drop = mk_drop(p, site(0, layer, 2), drop_on);
-    l2.res = A.Y, l2.gamma = P(w.ln2g), l2.beta = P(w.ln2b), l2.mask.valid = valid;
-    l2.y = Xout;
-    if (keep) l2.v_save = A.v2, l2.mean = A.m2, l2.rstd = A.r2;
-    linear_ln(A.H, L.fe, w.W2, L.fe, Me, d, L.fe, l2, s);
+    linear_ln(A.H, L.fe, w.W2, L.fe, Me, d, L.fe,
+              ln_fwd(enc_ln2_site(w, A, Me, valid, layer, drop_on), a.tmp, A.Y, Xout, keep), s);
   }
   // the region embedding and the shared norm (model.py:294): a.Aenc -> a.X[0]; keep as above
   void enc_embed_fwd(int Me, bool keep, hipStream_t s) {
-    LnFwd ln;
-    ln.M = Me, ln.d = L.d, ln.a = a.tmp, ln.gamma = P(L.enc_lng), ln.beta = P(L.enc_lnb), ln.y = a.X[0];
-    if (keep) ln.v_save = a.ev0, ln.mean = a.em0, ln.rstd = a.er0;
-    linear_ln(a.Aenc, L.Kp, L.enc_emb_W, L.Kp, Me, L.d, L.Kp, ln, s);
+    linear_ln(a.Aenc, L.Kp, L.enc_emb_W, L.Kp, Me, L.d, L.Kp, ln_fwd(enc_embed_site(Me), a.tmp, nullptr, a.X[0], keep), s);
   }
-  static constexpr int kImgLayer = 63;  // dropout-site layer index of encoder.image_encoder
 
   // split_image_objects (model.py:258-292, then the shared norm :294): a.Aenc -> a.X[0]
   void image_objects_fwd(int B, int N, bool drop_on, hipStream_t s) {
     const int Me = B * N, d = L.d;
     // LN([feats | pos] . W^T) per token; the pair rows only repeat rows, so embed each region once
-    LnFwd ln;
-    ln.M = Me, ln.d = d, ln.a = a.tmp, ln.gamma = P(L.enc_lng), ln.beta = P(L.enc_lnb);
-    ln.y = a.siY, ln.v_save = a.ev0, ln.mean = a.em0, ln.rstd = a.er0;
-    linear_ln(a.Aenc, L.Kp, L.enc_emb_W, L.Kp, Me, d, L.Kp, ln, s);
+    linear_ln(a.Aenc, L.Kp, L.enc_emb_W, L.Kp, Me, d, L.Kp, ln_fwd(enc_embed_site(Me), a.tmp, nullptr, a.siY), s);
     // the position embedding alone (added to the region token after the image block): the
     // position columns [F, Kp) of the packed input and weight (zero beyond F + P)
     linear(at(a.Aenc, L.F), L.Kp, L.enc_emb_W + L.F, L.Kp, a.siEp, d, act, Me, d, L.Kp - L.F, nullptr, 0, s);
     pair_gather(a.siY, a.valid, B, N, d, a.siX2, a.siValid, act, s);
     enc_layer_fwd(L.img, a.si, a.siX2, a.siZ, Me, 2, a.siValid, kImgLayer, drop_on, s);
     pair_take_add(a.siZ, a.siEp, Me, d, a.tmp, act, s);
-    LnFwd l2;
-    l2.M = Me, l2.d = d, l2.a = a.tmp, l2.gamma = P(L.enc_lng), l2.beta = P(L.enc_lnb);
-    l2.y = a.X[0], l2.v_save = a.siV, l2.mean = a.siM, l2.rstd = a.siR;
-    lnf(l2, s);
+    lnf(ln_fwd(img_norm2_site(Me), a.tmp, nullptr, a.X[0]), s);
   }
-  static constexpr int kMfLayer = 62;  // dropout-site layer index of the decoder's move-first FFN
 
   // move_first_image_feature (model.py:451-457): y = LN(x + drop(W2 relu(W1 (x + enc[:, 0]) + b1) + b2))
-  // over the M decoder rows in x (row r -> image r / rows_per_img, or r % bmod)
+  // over the M decoder rows in x (row r -> image r / rows_per_img, or r % bmod); keep = false
+  // (decoding): dropout off, nothing saved
   void move_first_fwd(const void* x, const void* enc, int M, int rows_per_img, int bmod, int N, void* U, void* H,
-                      void* tmp, void* y, void* v_save, float* mean, float* rstd, bool drop_on, hipStream_t s) {
+                      void* tmp, void* y, bool keep, bool drop_on, hipStream_t s) {
     const int dd = L.dd;
     add_first_region(x, enc, M, rows_per_img, bmod, N, dd, U, act, s);
     linear(U, dd, L.mf_W1, dd, H, L.fd, act, M, L.fd, dd, P(L.mf_b1), 1, s);
-    LnFwd ln;
-    ln.M = M, ln.d = dd, ln.a = tmp, ln.a_bias = P(L.mf_b2), ln.drop = mk_drop(cfg.dropout, site(1, kMfLayer, 0), drop_on);
-    ln.res = x, ln.gamma = P(L.mf_lng), ln.beta = P(L.mf_lnb), ln.y = y, ln.v_save = v_save, ln.mean = mean;
-    ln.rstd = rstd;
-    linear_ln(H, L.fd, L.mf_W2, L.fd, M, dd, L.fd, ln, s);
+    linear_ln(H, L.fd, L.mf_W2, L.fd, M, dd, L.fd, ln_fwd(move_first_site(M, drop_on), tmp, x, y, keep), s);
   }
   // the decoder output the classifier reads
   void* dec_out() const { return L.has_mf ? a.mfOut : a.D[L.Ld]; }
@@ -831,14 +929,12 @@ struct capgen_engine {
     require(B >= 1 && N >= 1 && T >= 2, "forward: need B>=1, N>=1, T>=2");
     require(N <= 64 && T - 1 <= L.maxlen - 1, "forward: N must be <= 64 and T <= max_length");
     const int Lq = T - 1, Me = B * N, Md = B * Lq, d = L.d, dd = L.dd;
-    const int He = L.He, Hd = L.Hd, dke = d / He, dkd = dd / Hd;
     fB = B, fN = N, fT = T, fwd_drop = drop_on;
     stamp_next = 0;
-    const float p = cfg.dropout, pa = cfg.attention_dropout;
 
     // (+ the dropout seed advance when dropout is on: the pack kernel does not read the seed, every
     // dropout site of this forward runs after this launch)
-    pack_encoder_input(feats, ft, pos, Me, L.F, L.P, L.Kp, a.Aenc, act, a.valid, s, in_idx, N, in_n_img,
+    pack_encoder_input(feats, ft, pos, Me, L.F, L.P, L.Kp, a.Aenc, act, a.valid, s, in.idx, N, in.n_img,
                        drop_on ? seed : nullptr);
     // caption ids / targets / count: with the decoder front on es2 (and no count all-reduce, which
     // stays on the critical stream) the prep runs there too, first thing of the front
@@ -859,35 +955,21 @@ struct capgen_engine {
     // ---- decoder front (model.py:432-436 and block 0's self-attention half + cross query,
     // modules.py:185-197): depends on the captions only, so with overlap_front it runs on es2
     // beside the whole encoder and joins before block 0's cross attention
-    RowMask dmask{};
-    dmask.ids = a.ids, dmask.pad_idx = cfg.pad_idx;
     const bool front = overlap_front && es2 != s;
     auto dec_embed = [&](void* tmp, hipStream_t fs) {
       embedding_gather(P(L.emb), a.ids, 1, Md, L.dwe, a.E, act, fs, L.V);
-      LnFwd ln;
-      ln.M = Md, ln.d = dd, ln.a = tmp, ln.pe = pe, ln.pe_L = Lq, ln.gamma = P(L.dec_lng), ln.beta = P(L.dec_lnb);
-      ln.y = a.D[0], ln.v_save = a.dv0, ln.mean = a.dm0, ln.rstd = a.dr0;
+      LnFwd ln = ln_fwd(dec_embed_site(Md), tmp, nullptr, a.D[0]);
+      ln.pe = pe, ln.pe_L = Lq;
       linear_ln(a.E, L.dwe, L.Wel, L.dwe, Md, dd, L.dwe, ln, fs);
     };
-    // self attention: key-pad(ids) OR causal (model.py:421-430), then the cross-attention query
+    // self attention, then the cross-attention query
     // q_proj: also the cross-attention query projection (else the fused cross-attention launch does it)
     auto dec_self_half = [&](int l, void* tmp, hipStream_t fs, bool q_proj) {
       const auto& w = L.dec[l];
       auto& A = a.dec[l];
-      AttnGeom g;
-      g.B = B, g.H = Hd, g.Lq = Lq, g.Lk = Lq, g.dk = dkd;
-      g.q = A.qkv, g.q_ld = 3 * dd, g.q_bs = (int64_t)Lq * 3 * dd;
-      g.k = at(A.qkv, dd), g.k_ld = 3 * dd, g.k_bs = (int64_t)Lq * 3 * dd;
-      g.v = at(A.qkv, 2 * dd), g.v_ld = 3 * dd, g.v_bs = (int64_t)Lq * 3 * dd;
-      g.o_ld = dd, g.o_bs = (int64_t)Lq * dd;
-      g.key_ids = a.ids, g.kid_bs = Lq, g.pad_idx = cfg.pad_idx, g.causal = 1;
-      g.temperature = std::sqrt((float)dkd);
-      g.drop = mk_drop(pa, site(1, l, 3), drop_on);
+      const AttnGeom g = dec_self_geom(l, B, Lq, drop_on);
       self_attention(a.D[l], w.Wqkv, Md, dd, g, A.qkv, A.atts, keep_probs(g) ? A.Ps : nullptr, fs);
-      LnFwd l1;
-      l1.M = Md, l1.d = dd, l1.a = tmp, l1.drop = mk_drop(p, site(1, l, 4), drop_on), l1.res = a.D[l];
-      l1.gamma = P(w.lsg), l1.beta = P(w.lsb), l1.y = A.D1, l1.v_save = A.vs, l1.mean = A.ms, l1.rstd = A.rs;
-      linear_ln(A.atts, dd, w.Wo_s, dd, Md, dd, dd, l1, fs);
+      linear_ln(A.atts, dd, w.Wo_s, dd, Md, dd, dd, ln_fwd(dec_self_site(l, Md, drop_on), tmp, a.D[l], A.D1), fs);
       if (q_proj) linear(A.D1, dd, w.Wq_c, dd, A.qc, dd, act, Md, dd, dd, nullptr, 0, fs);
     };
     if (front) {
@@ -915,37 +997,21 @@ struct capgen_engine {
     // ---- decoder (model.py:419-459) ----
     if (front && fj > L.Le) hz::wait(s, ev_fj);
     else if (!front) dec_embed(a.tmp, s);
-    const int64_t kvld = (int64_t)L.Ld * 2 * dd;
     for (int l = 0; l < L.Ld; ++l) {
       const auto& w = L.dec[l];
       auto& A = a.dec[l];
       const bool q_done = front && l == 0;  // block 0's query was projected on es2 with the front
       if (!q_done) dec_self_half(l, a.tmp, s, !cross_fusable(Lq));
-      // cross attention over the encoder output, context mask = region key-pad (model.py:82)
-      AttnGeom c;
-      c.B = B, c.H = Hd, c.Lq = Lq, c.Lk = N, c.dk = dkd;
-      c.q = A.qc, c.q_ld = dd, c.q_bs = (int64_t)Lq * dd;
-      c.k = at(a.KV, (int64_t)l * 2 * dd), c.k_ld = kvld, c.k_bs = (int64_t)N * kvld;
-      c.v = at(a.KV, (int64_t)l * 2 * dd + dd), c.v_ld = kvld, c.v_bs = (int64_t)N * kvld;
-      c.o_ld = dd, c.o_bs = (int64_t)Lq * dd;
-      c.key_valid = a.valid, c.kv_bs = N;
-      c.temperature = std::sqrt((float)dkd);
-      c.drop = mk_drop(pa, site(1, l, 5), drop_on);
+      // cross attention over the encoder output
+      const AttnGeom c = dec_cross_geom(l, B, Lq, N, drop_on);
       cross_attention(c, A.D1, w.Wq_c, dd, A.qc, A.attc, keep_probs(c) ? A.Pc : nullptr, q_done || !cross_fusable(Lq), s);
-      LnFwd l2;
-      l2.M = Md, l2.d = dd, l2.a = a.tmp, l2.drop = mk_drop(p, site(1, l, 6), drop_on), l2.res = A.D1;
-      l2.gamma = P(w.lcg), l2.beta = P(w.lcb), l2.y = A.D2, l2.v_save = A.vc, l2.mean = A.mc, l2.rstd = A.rc;
-      linear_ln(A.attc, dd, w.Wo_c, dd, Md, dd, dd, l2, s);
-      // FFN, then x non_pad (modules.py:201-204)
+      linear_ln(A.attc, dd, w.Wo_c, dd, Md, dd, dd, ln_fwd(dec_cross_site(l, Md, drop_on), a.tmp, A.D1, A.D2), s);
+      // FFN
       linear(A.D2, dd, w.W1, dd, A.H, L.fd, act, Md, L.fd, dd, P(w.b1), 1, s);
-      LnFwd l3;
-      l3.M = Md, l3.d = dd, l3.a = a.tmp, l3.a_bias = P(w.b2), l3.drop = mk_drop(p, site(1, l, 7), drop_on);
-      l3.res = A.D2, l3.gamma = P(w.lfg), l3.beta = P(w.lfb), l3.mask = dmask;
-      l3.y = a.D[l + 1], l3.v_save = A.vf, l3.mean = A.mf, l3.rstd = A.rf;
-      linear_ln(A.H, L.fd, w.W2, L.fd, Md, dd, L.fd, l3, s);
+      linear_ln(A.H, L.fd, w.W2, L.fd, Md, dd, L.fd, ln_fwd(dec_ffn_site(l, Md, drop_on), a.tmp, A.D2, a.D[l + 1]), s);
     }
     if (L.has_mf)
-      move_first_fwd(a.D[L.Ld], a.X[L.Le], Md, Lq, 0, N, a.mfU, a.mfH, a.tmp, a.mfOut, a.mfV, a.mfM, a.mfR, drop_on, s);
+      move_first_fwd(a.D[L.Ld], a.X[L.Le], Md, Lq, 0, N, a.mfU, a.mfH, a.tmp, a.mfOut, /*keep=*/true, drop_on, s);
     // ---- classifier + CE (model.py:93-96) ----
     if (fused_ce()) {
       // the logits are never written: the GEMM epilogue leaves exp(v - slab max) + slab stats,
@@ -957,10 +1023,10 @@ struct capgen_engine {
       if (stamp_on) ga.stamp = stamp(s, "gemm classifier+CE " + dims(Md, L.V, dd));
       gemm(ga, act, act, false, false, s);
       ce_finish(a.ce_stats, (L.V + 15) / 16, a.ce_tl, a.tgt, Md, L.V, cfg.pad_idx, a.loss_row,
-                reinterpret_cast<bf16*>(a.dlogits), s, in_w, Lq);
+                reinterpret_cast<bf16*>(a.dlogits), s, in.w, Lq);
     } else {
       linear(dec_out(), dd, L.Wc, dd, a.logits, L.V, DType::F32, Md, L.V, dd, P(L.bc), 0, s);
-      cross_entropy_rows(a.logits, a.tgt, Md, L.V, cfg.pad_idx, a.loss_row, a.dlogits, act, s, in_w, Lq);
+      cross_entropy_rows(a.logits, a.tgt, Md, L.V, cfg.pad_idx, a.loss_row, a.dlogits, act, s, in.w, Lq);
     }
     float* lo = loss_out ? loss_out : a.loss;
     last_loss = lo;
@@ -1229,41 +1295,25 @@ struct capgen_engine {
   // backward of enc_layer_fwd: gO = grad wrt Xout on entry, grad wrt X on exit; gR scratch
   void enc_layer_bwd(const EncLayerOff& w, EncAct& A, Acts::GradBufs& gb, const void* X, int B, int N,
                      const uint8_t* valid, int layer, bool on, void* gO, void* gR, hipStream_t s) {
-    const int Me = B * N, d = L.d, He = L.He, dke = d / He;
-    void* go = gO;
-    const float p = cfg.dropout, pa = cfg.attention_dropout;
-    RowMask mask{};
-    mask.valid = valid;
-    const LnBwd lffn = lnb_desc(Me, d, gO, A.v2, A.m2, A.r2, w.ln2g, w.ln2b, w.b2, mask, mk_drop(p, site(0, layer, 2), on),
-                                gR, gb.gAf);
-    const LnBwd lmha = lnb_desc(Me, d, gR, A.v1, A.m1, A.r1, w.ln1g, w.ln1b, -1, RowMask{},
-                                mk_drop(p, site(0, layer, 1), on), go, gb.gA1);
+    const int Me = B * N, d = L.d;
+    const LnBwd lffn = ln_bwd(enc_ln2_site(w, A, Me, valid, layer, on), gO, gR, gb.gAf);
+    const LnBwd lmha = ln_bwd(enc_ln1_site(w, A, Me, layer, on), gR, gO, gb.gA1);
     ffn_bwd(Me, d, L.fe, lffn, A.Y, A.H, w.W1, w.b1, w.W2, gb.gH, s);  // gR = grad wrt Y
-    AttnGeom g;
-    g.B = B, g.H = He, g.Lq = N, g.Lk = N, g.dk = dke;
-    g.q = A.qkv, g.q_ld = 3 * d, g.q_bs = (int64_t)N * 3 * d;
-    g.k = at(A.qkv, d), g.k_ld = 3 * d, g.k_bs = (int64_t)N * 3 * d;
-    g.v = at(A.qkv, 2 * d), g.v_ld = 3 * d, g.v_bs = (int64_t)N * 3 * d;
-    g.o_ld = d, g.o_bs = (int64_t)N * d;
-    if (valid) g.key_valid = valid, g.kv_bs = N, g.causal = 1;
-    g.temperature = std::sqrt((float)dke);
-    g.drop = mk_drop(pa, site(0, layer, 0), on);
-    mha_bwd(Me, d, lmha, A.att, w.Wo, gb.gATT1, g, A.P, gb.gQKV, at(gb.gQKV, d), at(gb.gQKV, 2 * d), s);
+    mha_bwd(Me, d, lmha, A.att, w.Wo, gb.gATT1, enc_self_geom(A, B, N, valid, layer, on), A.P, gb.gQKV,
+            at(gb.gQKV, d), at(gb.gQKV, 2 * d), s);
     dw_side(gb.gQKV, 3 * d, X, d, w.Wqkv, d, Me, 3 * d, d, nullptr, s);
-    linear_dx(gb.gQKV, 3 * d, w.Wqkv, d, go, d, Me, 3 * d, d, 1, nullptr, nullptr, s);  // gO = grad wrt X
+    linear_dx(gb.gQKV, 3 * d, w.Wqkv, d, gO, d, Me, 3 * d, d, 1, nullptr, nullptr, s);  // gO = grad wrt X
   }
 
   // backward of image_objects_fwd: gX0 = grad wrt a.X[0] -> embedding weight gradient
   void image_objects_bwd(const void* gX0, int B, int N, bool on, hipStream_t s) {
     const int Me = B * N, d = L.d;
     // second norm: grad wrt Z[2r+1] + Ep[r] (no residual, no dropout)
-    lnb(lnb_desc(Me, d, gX0, a.siV, a.siM, a.siR, L.enc_lng, L.enc_lnb, -1, RowMask{}, Drop{}, nullptr,
-                           a.siGEp), s);
+    lnb(ln_bwd(img_norm2_site(Me), gX0, nullptr, a.siGEp), s);
     pair_scatter(a.siGEp, Me, d, a.siG0, act, s);  // only the region token's output is kept
     enc_layer_bwd(L.img, a.si, a.gsi, a.siX2, Me, 2, a.siValid, kImgLayer, on, a.siG0, a.siG1, s);
     pair_reduce(a.siG0, B, N, d, a.siGY, act, s);  // image-row tokens fold back onto region 0
-    lnb(lnb_desc(Me, d, a.siGY, a.ev0, a.em0, a.er0, L.enc_lng, L.enc_lnb, -1, RowMask{}, Drop{}, nullptr,
-                           a.gAe), s);
+    lnb(ln_bwd(enc_embed_site(Me), a.siGY, nullptr, a.gAe), s);
     // feature columns see the first embedding only; position columns both (+ Ep after the block)
     linear_dw(a.gAe, d, a.Aenc, L.Kp, L.enc_emb_W, L.Kp, Me, d, L.F, nullptr, s);
     add_inplace(a.siGEp, a.gAe, (int64_t)Me * d, act, s);
@@ -1274,9 +1324,7 @@ struct capgen_engine {
   // (residual + U), a.mfGU = grad wrt U
   void move_first_bwd(int Md, bool on, hipStream_t s) {
     const int dd = L.dd, fd = L.fd;
-    const LnBwd lb = lnb_desc(Md, dd, a.gOut, a.mfV, a.mfM, a.mfR, L.mf_lng, L.mf_lnb, L.mf_b2, RowMask{},
-                              mk_drop(cfg.dropout, site(1, kMfLayer, 0), on), a.gRes, a.mfGA);
-    lnb(lb, s);
+    lnb(ln_bwd(move_first_site(Md, on), a.gOut, a.gRes, a.mfGA), s);
     dw_side(a.mfGA, dd, a.mfH, fd, L.mf_W2, fd, Md, dd, fd, nullptr, s);
     linear_dx(a.mfGA, dd, L.mf_W2, fd, a.mfGH, fd, Md, dd, fd, 0, a.mfH, nullptr, s, GS(L.mf_b1));
     dw_side(a.mfGH, fd, a.mfU, dd, L.mf_W1, dd, Md, fd, dd, nullptr, s);
@@ -1292,9 +1340,7 @@ struct capgen_engine {
     grads_sharded = false;
     stamp_next = stamp_fwd_end;
     const int B = fB, N = fN, Lq = fT - 1, Me = B * N, Md = B * Lq, d = L.d, dd = L.dd;
-    const int He = L.He, Hd = L.Hd, dke = d / He, dkd = dd / Hd;
     const bool on = fwd_drop;
-    const float p = cfg.dropout, pa = cfg.attention_dropout;
     // the striped LN/bias partials start at 0 (the critical stream's first LayerNorm backward adds
     // into them); the accumulated word-embedding gradient (20 MB at C2) is zeroed on es2 after the
     // fork below -- its only writer is the embedding scatter on es2
@@ -1314,34 +1360,6 @@ struct capgen_engine {
       adam_prepare(step, cfg.lr, cfg.beta1, cfg.beta2, adam_scal, cst == hipStreamCaptureStatusNone ? ec : s);
       zbuckets.clear();
     }
-
-    RowMask dmask{};
-    dmask.ids = a.ids, dmask.pad_idx = cfg.pad_idx;
-    // the LayerNorm backward of every block (model.py:86-90, 114-120 restated backward)
-    auto dec_ffn_lb = [&](int l, const void* dy, void* dres) {
-      const auto& A = a.dec[l];
-      const auto& w = L.dec[l];
-      return lnb_desc(Md, dd, dy, A.vf, A.mf, A.rf, w.lfg, w.lfb, w.b2, dmask, mk_drop(p, site(1, l, 7), on), dres,
-                      a.gdec[l].gAf);
-    };
-    auto dec_cross_lb = [&](int l, const void* dy, void* dres) {
-      const auto& A = a.dec[l];
-      const auto& w = L.dec[l];
-      return lnb_desc(Md, dd, dy, A.vc, A.mc, A.rc, w.lcg, w.lcb, -1, RowMask{}, mk_drop(p, site(1, l, 6), on), dres,
-                      a.gdec[l].gA2);
-    };
-    auto dec_self_lb = [&](int l, const void* dy, void* dres) {
-      const auto& A = a.dec[l];
-      const auto& w = L.dec[l];
-      return lnb_desc(Md, dd, dy, A.vs, A.ms, A.rs, w.lsg, w.lsb, -1, RowMask{}, mk_drop(p, site(1, l, 4), on), dres,
-                      a.gdec[l].gA1);
-    };
-    auto dec_emb_lb = [&](const void* dy) {  // LN(E.Wel^T + PE) (model.py:432-436): no residual, no dropout
-      return lnb_desc(Md, dd, dy, a.dv0, a.dm0, a.dr0, L.dec_lng, L.dec_lnb, -1, RowMask{}, Drop{}, nullptr, a.gAd);
-    };
-    auto enc_emb_lb = [&](const void* dy) {
-      return lnb_desc(Me, d, dy, a.ev0, a.em0, a.er0, L.enc_lng, L.enc_lnb, -1, RowMask{}, Drop{}, nullptr, a.gAe);
-    };
 
     // classifier: dlogits are unscaled (softmax - onehot); grad_scale folds 1/count (+focal).  The
     // critical stream goes straight from the forward into the dX GEMM: the side work (weight and bias
@@ -1369,42 +1387,26 @@ struct capgen_engine {
       const auto& w = L.dec[l];
       auto& A = a.dec[l];
       auto& gb = a.gdec[l];
-      const LnBwd lffn = dec_ffn_lb(l, gO, gR), lcross = dec_cross_lb(l, gR, gO), lself = dec_self_lb(l, gO, gR);
+      const LnBwd lffn = ln_bwd(dec_ffn_site(l, Md, on), gO, gR, gb.gAf);
+      const LnBwd lcross = ln_bwd(dec_cross_site(l, Md, on), gR, gO, gb.gA2);
+      const LnBwd lself = ln_bwd(dec_self_site(l, Md, on), gO, gR, gb.gA1);
       ffn_bwd(Md, dd, L.fd, lffn, A.D2, A.H, w.W1, w.b1, w.W2, gb.gH, s);  // gR = grad wrt D2
-      AttnGeom c;
-      c.B = B, c.H = Hd, c.Lq = Lq, c.Lk = N, c.dk = dkd;
-      c.q = A.qc, c.q_ld = dd, c.q_bs = (int64_t)Lq * dd;
-      c.k = at(a.KV, (int64_t)l * 2 * dd), c.k_ld = kvld, c.k_bs = (int64_t)N * kvld;
-      c.v = at(a.KV, (int64_t)l * 2 * dd + dd), c.v_ld = kvld, c.v_bs = (int64_t)N * kvld;
-      c.o_ld = dd, c.o_bs = (int64_t)Lq * dd;
-      c.key_valid = a.valid, c.kv_bs = N;  // masks as in forward (the MFMA backward recomputes P)
-      c.temperature = std::sqrt((float)dkd);
-      c.drop = mk_drop(pa, site(1, l, 5), on);
       // (lcross.d_res = grad wrt D1, the residual part)
-      mha_bwd(Md, dd, lcross, A.attc, w.Wo_c, gb.gATT2, c, A.Pc, gb.gQc, at(a.gKV, (int64_t)l * 2 * dd),
-              at(a.gKV, (int64_t)l * 2 * dd + dd), s);
+      mha_bwd(Md, dd, lcross, A.attc, w.Wo_c, gb.gATT2, dec_cross_geom(l, B, Lq, N, on), A.Pc, gb.gQc,
+              at(a.gKV, (int64_t)l * 2 * dd), at(a.gKV, (int64_t)l * 2 * dd + dd), s);
       // block 0: the rest of the block runs on es2 (ov), the encoder chain starts on s below
       const bool ov = l == 0 && overlap_dec0 && es2 != s;
       const hipStream_t hs = ov ? es2 : s;
       if (ov) flush(s);  // es2 waits for block 0's cross-attention backward; queued dW issued
       dw_side(gb.gQc, dd, A.D1, dd, w.Wq_c, dd, Md, dd, dd, nullptr, hs);
       linear_dx(gb.gQc, dd, w.Wq_c, dd, gO, dd, Md, dd, dd, 1, nullptr, nullptr, hs);  // gO = grad wrt D1
-      AttnGeom g;
-      g.B = B, g.H = Hd, g.Lq = Lq, g.Lk = Lq, g.dk = dkd;
-      g.q = A.qkv, g.q_ld = 3 * dd, g.q_bs = (int64_t)Lq * 3 * dd;
-      g.k = at(A.qkv, dd), g.k_ld = 3 * dd, g.k_bs = (int64_t)Lq * 3 * dd;
-      g.v = at(A.qkv, 2 * dd), g.v_ld = 3 * dd, g.v_bs = (int64_t)Lq * 3 * dd;
-      g.o_ld = dd, g.o_bs = (int64_t)Lq * dd;
-      g.key_ids = a.ids, g.kid_bs = Lq, g.pad_idx = cfg.pad_idx, g.causal = 1;  // as in forward
-      g.temperature = std::sqrt((float)dkd);
-      g.drop = mk_drop(pa, site(1, l, 3), on);
       // (lself.d_res = grad wrt D_l, the residual part)
-      mha_bwd(Md, dd, lself, A.atts, w.Wo_s, gb.gATT1, g, A.Ps, gb.gQKV, at(gb.gQKV, dd), at(gb.gQKV, 2 * dd), hs);
+      mha_bwd(Md, dd, lself, A.atts, w.Wo_s, gb.gATT1, dec_self_geom(l, B, Lq, on), A.Ps, gb.gQKV, at(gb.gQKV, dd),
+              at(gb.gQKV, 2 * dd), hs);
       dw_side(gb.gQKV, 3 * dd, a.D[l], dd, w.Wqkv, dd, Md, 3 * dd, dd, nullptr, hs);
       linear_dx(gb.gQKV, 3 * dd, w.Wqkv, dd, gR, dd, Md, 3 * dd, dd, 1, nullptr, nullptr, hs);
       if (l % bucket_blocks == 0)  // blocks l .. l + bucket_blocks - 1 (contiguous in the arena)
-        (ov || l == 0 ? bucket(w.Wqkv, dec_end(std::min(l + bucket_blocks - 1, L.Ld - 1)) - w.Wqkv, hs)
-                      : bucket(w.Wqkv, dec_end(std::min(l + bucket_blocks - 1, L.Ld - 1)) - w.Wqkv, hs));
+        bucket(w.Wqkv, dec_end(std::min(l + bucket_blocks - 1, L.Ld - 1)) - w.Wqkv, hs);
       if (ov) dec0_on_side = true;
       std::swap(gO, gR);  // gO = grad wrt D_l
     }
@@ -1415,7 +1417,7 @@ struct capgen_engine {
     dec0_on_side = false;
     // decoder embedding: LN(E.Wel^T + PE) (model.py:432-436) -- off the critical path
     {
-      const LnBwd lb = dec_emb_lb(gO);
+      const LnBwd lb = ln_bwd(dec_embed_site(Md), gO, nullptr, a.gAd);
       flush(s);
       lnb(lb, es2);
       linear_dx(a.gAd, dd, L.Wel, L.dwe, a.gE, L.dwe, Md, dd, L.dwe, 0, nullptr, nullptr, es2);
@@ -1443,9 +1445,7 @@ struct capgen_engine {
     for (int l = L.Le - 1; l >= 0; --l) {
       const auto& w = L.enc[l];
       enc_layer_bwd(w, a.enc[l], a.genc[l], a.X[l], B, N, cfg.encode_mask ? a.valid : nullptr, l, on, gO, gR, s);
-      if (l % bucket_blocks == 0)
-        (l == 0 ? bucket(w.Wqkv, enc_end(std::min(l + bucket_blocks - 1, L.Le - 1)) - w.Wqkv, s)
-                : bucket(w.Wqkv, enc_end(std::min(l + bucket_blocks - 1, L.Le - 1)) - w.Wqkv, s));
+      if (l % bucket_blocks == 0) bucket(w.Wqkv, enc_end(std::min(l + bucket_blocks - 1, L.Le - 1)) - w.Wqkv, s);
     }
     // the tail of the step's dependency chain: the encoder-embedding LayerNorm backward and
     // weight gradient, then its Adam, which the next forward's first GEMM needs -- on the
@@ -1455,7 +1455,7 @@ struct capgen_engine {
       image_objects_bwd(gO, B, N, on, s);
       flush(s);  // the image block's weight gradients share the embedding bucket
     } else {
-      lnb(enc_emb_lb(gO), s);
+      lnb(ln_bwd(enc_embed_site(Me), gO, nullptr, a.gAe), s);
       linear_dw(a.gAe, d, a.Aenc, L.Kp, L.enc_emb_W, L.Kp, Me, d, L.Kp, nullptr, s);
     }
     // every encoder LayerNorm/bias partial was accumulated on s; in step mode the fold and the
@@ -1578,7 +1578,7 @@ struct capgen_engine {
   void train_step(const void* f, DType ft, const float* pos, const int32_t* caps, int B, int N, int T, float* loss,
                   hipStream_t cs) {
     ensure_acts(B, N, T);
-    Key k{f, pos, caps, loss, (int)ft, B, N, T, training, in_idx, in_n_img, in_w};
+    Key k{f, pos, caps, loss, (int)ft, B, N, T, training, in};
     // (the hazard checker's log runs the eager forward: the graph replays the same launches)
     // under DP the forward graph holds the count and partial-CE all-reduces (RCCL ops capture);
     // a host-set global count (capgen_dp_set_global_count) runs the forward eagerly instead --
@@ -1679,12 +1679,6 @@ struct capgen_engine {
     leave(cs);
   }
   int rl_B = 0;
-  // resident feature store: when set, forward() gathers image in_idx[b] from feats/pos
-  const int32_t* in_idx = nullptr;
-  int in_n_img = 0;
-  // per-caption loss weights [B] (capgen_train_step_weighted): when set, forward()'s CE scales caption
-  // b's loss rows and logit gradients by in_w[b]; the count stays the number of non-pad targets
-  const float* in_w = nullptr;
 
   // ------------------------------------------------------------------------------------
   // decoding (model.py:101-200), KV-cached.  Bit-identical to recomputing the prefix: row
@@ -1802,7 +1796,7 @@ struct capgen_engine {
     lnf(ln, s);
     RowMask rm{};
     rm.ids = ids + t, rm.ids_ld = Tc, rm.pad_idx = cfg.pad_idx;
-    const int64_t kvld = (int64_t)L.Ld * 2 * dd, cld = (int64_t)Tc * 2 * dd;
+    const int64_t cld = (int64_t)Tc * 2 * dd;
     const int fmode = ln_fold(R);
     const bool fold = fmode == 2, fold1 = fmode >= 1;  // every site / the cross-query site
     for (int l = 0; l < L.Ld; ++l) {
@@ -1847,12 +1841,7 @@ struct capgen_engine {
         linear(g.x1, dd, w.Wq_c, dd, g.q, dd, act, R, dd, dd, nullptr, 0, s, DT(w.Wq_c));
       }
       const bool want_p = want_attn && l == L.Ld - 1;
-      AttnGeom c;  // rows r -> image r % Bimg
-      c.H = Hd, c.Lk = N, c.dk = dkd;
-      c.k = at(a.KV, (int64_t)l * 2 * dd), c.k_ld = kvld, c.k_bs = (int64_t)N * kvld;
-      c.v = at(a.KV, (int64_t)l * 2 * dd + dd), c.v_ld = kvld, c.v_bs = (int64_t)N * kvld;
-      c.key_valid = a.valid, c.kv_bs = N;
-      c.temperature = std::sqrt((float)dkd);
+      AttnGeom c = cross_kv(l, N);  // rows r -> image r % Bimg
       const int kb = R / Bimg;  // beam rows per image: row j * Bimg + b
       if (act == DType::BF16 && cross_mfma_on && !want_p && kb > 1 && R % Bimg == 0 && kb <= 64) {
         // an image's kb beam rows as ONE query block of the MFMA attention (attention_mfma.hip), one
@@ -1893,7 +1882,7 @@ struct capgen_engine {
     }
     const void* xo = g.x;
     if (L.has_mf) {  // rows r -> image r % Bimg
-      move_first_fwd(g.x, a.X[L.Le], R, 1, Bimg, N, g.x2, g.h, g.tmp, g.x1, nullptr, nullptr, nullptr, false, s);
+      move_first_fwd(g.x, a.X[L.Le], R, 1, Bimg, N, g.x2, g.h, g.tmp, g.x1, /*keep=*/false, /*drop_on=*/false, s);
       xo = g.x1;
     }
     if (slab_decode()) {  // f32 logits + per-16-column-slab {max, exp-sum} for the selection
@@ -2467,9 +2456,8 @@ int capgen_train_step_indexed(capgen_t* h, const void* feat_store, int feats_dty
   return guarded([&] {
     set_device(h);
     require(n_images >= 1, "train_step_indexed: empty store");
-    h->in_n_img = n_images;
     {
-      Scoped<const int32_t*> indexed(h->in_idx, img_idx);
+      Scoped<StepIn> inputs(h->in, StepIn{img_idx, n_images, nullptr});
       h->train_step(feat_store, dt(feats_dtype), pos_store, caps, B, N, T, loss_out, (hipStream_t)stream);
     }
     h->dp_check((hipStream_t)stream, loss_out);
@@ -2486,9 +2474,7 @@ int capgen_train_step_weighted(capgen_t* h, const void* feats, int feats_dtype, 
     require(!img_idx || n_images >= 1, "train_step_weighted: empty store");
     hipStream_t cs = (hipStream_t)stream;
     const DType ft = dt(feats_dtype);
-    if (img_idx) h->in_n_img = n_images;
-    Scoped<const int32_t*> indexed(h->in_idx, img_idx);
-    Scoped<const float*> weighted(h->in_w, weights);
+    Scoped<StepIn> inputs(h->in, StepIn{img_idx, img_idx ? n_images : 0, weights});
     if (train) {
       h->train_step(feats, ft, pos, caps, B, N, T, loss_out, cs);
       h->dp_check(cs, loss_out);
@@ -2554,12 +2540,7 @@ int capgen_debug_attention(int dtype, int B, int H, int Lq, int Lk, int dk, cons
   return guarded([&] {
     require(B >= 1 && H >= 1 && dk >= 1, "debug_attention: bad shape");
     const int64_t ld = (int64_t)H * dk;
-    AttnGeom g;
-    g.B = B, g.H = H, g.Lq = Lq, g.Lk = Lk, g.dk = dk;
-    g.q = q, g.q_ld = ld, g.q_bs = Lq * ld;
-    g.k = k, g.k_ld = ld, g.k_bs = Lk * ld;
-    g.v = v, g.v_ld = ld, g.v_bs = Lk * ld;
-    g.o_ld = ld, g.o_bs = Lq * ld;
+    AttnGeom g = attn_dense(B, H, Lq, Lk, dk, q, ld, k, ld, v, ld, ld);
     g.key_valid = key_valid, g.kv_bs = Lk;
     g.causal = causal;
     g.temperature = temperature;
@@ -2592,13 +2573,8 @@ int capgen_debug_qkv_attention(int B, int L, int H, const void* X, const void* W
     const int d = H * 64;
     QkvAttn qa;
     AttnGeom& g = qa.g;
-    g.B = B, g.H = H, g.Lq = L, g.Lk = L, g.dk = 64;
-    g.q = qkv, g.q_ld = 3 * d, g.q_bs = (int64_t)L * 3 * d;
-    g.k = (const bf16*)qkv + d, g.k_ld = 3 * d, g.k_bs = (int64_t)L * 3 * d;
-    g.v = (const bf16*)qkv + 2 * d, g.v_ld = 3 * d, g.v_bs = (int64_t)L * 3 * d;
-    g.o_ld = d, g.o_bs = (int64_t)L * d;
+    g = attn_dense(B, H, L, L, 64, qkv, 3 * d, (const bf16*)qkv + d, 3 * d, (const bf16*)qkv + 2 * d, 3 * d, d);
     g.key_valid = key_valid, g.kv_bs = L, g.key_ids = key_ids, g.kid_bs = L, g.pad_idx = pad_idx, g.causal = causal;
-    g.temperature = 8.f;  // sqrt(64)
     qa.X = (const bf16*)X, qa.ldx = d, qa.W = debug_tiles((const bf16*)W, 3 * d, (hipStream_t)stream), qa.d = d;
     qa.qkv = (bf16*)qkv, qa.ldqkv = 3 * d, qa.o = (bf16*)o;
     qkv_attn_fwd(qa, (hipStream_t)stream);
@@ -2611,14 +2587,8 @@ int capgen_debug_cross_attention(int B, int Lq, int Lk, int H, const void* X, co
     require(B >= 1 && Lq >= 1 && Lk >= 1 && H >= 1, "debug_cross_attention: bad shape");
     const int d = H * 64;
     QkvAttn qa;
-    AttnGeom& g = qa.g;
-    g.B = B, g.H = H, g.Lq = Lq, g.Lk = Lk, g.dk = 64;
-    g.q = q, g.q_ld = d, g.q_bs = (int64_t)Lq * d;
-    g.k = KV, g.k_ld = 2 * d, g.k_bs = (int64_t)Lk * 2 * d;
-    g.v = (const bf16*)KV + d, g.v_ld = 2 * d, g.v_bs = (int64_t)Lk * 2 * d;
-    g.o_ld = d, g.o_bs = (int64_t)Lq * d;
-    g.key_valid = key_valid, g.kv_bs = Lk;
-    g.temperature = 8.f;
+    qa.g = attn_dense(B, H, Lq, Lk, 64, q, d, KV, 2 * d, (const bf16*)KV + d, 2 * d, d);
+    qa.g.key_valid = key_valid, qa.g.kv_bs = Lk;
     qa.cross = 1;
     qa.X = (const bf16*)X, qa.ldx = d, qa.W = debug_tiles((const bf16*)Wq, d, (hipStream_t)stream), qa.d = d;
     qa.qkv = (bf16*)q, qa.ldqkv = d, qa.o = (bf16*)o;
@@ -2638,14 +2608,9 @@ int capgen_debug_attention_bwd_wo(int B, int Lq, int Lk, int H, const void* q, c
     qkv_tile_weights_t((const bf16*)Wo, 512, wt, s);
     QkvBwd qb;
     AttnGeom& g = qb.g;
-    g.B = B, g.H = H, g.Lq = Lq, g.Lk = Lk, g.dk = 64;
-    g.q = q, g.q_ld = d, g.q_bs = (int64_t)Lq * d;
-    g.k = k, g.k_ld = d, g.k_bs = (int64_t)Lk * d;
-    g.v = v, g.v_ld = d, g.v_bs = (int64_t)Lk * d;
-    g.o_ld = d, g.o_bs = (int64_t)Lq * d;
+    g = attn_dense(B, H, Lq, Lk, 64, q, d, k, d, v, d, d);
     if (key_valid) g.key_valid = key_valid, g.kv_bs = Lk;
     g.causal = causal;
-    g.temperature = 8.f;
     qb.dA = (const bf16*)dA, qb.ldda = d, qb.Wt = wt;
     qb.dq = (bf16*)dq, qb.dk = (bf16*)dk, qb.dv = (bf16*)dv;
     qkv_attn_bwd(qb, s);
