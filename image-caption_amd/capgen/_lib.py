@@ -61,6 +61,10 @@ _SIGS = {
     "capgen_set_training": (C.c_int, [_P, C.c_int]),
     "capgen_set_graph": (C.c_int, [_P, C.c_int]),
     "capgen_set_decode_log_softmax": (C.c_int, [_P, C.c_int]),
+    "capgen_set_lr": (C.c_int, [_P, C.c_float]),
+    "capgen_get_lr": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "capgen_set_grad_clip": (C.c_int, [_P, C.c_float]),
+    "capgen_last_grad_norm": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "capgen_forward": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "capgen_backward": (C.c_int, [_P, _P]),
     "capgen_adam_step": (C.c_int, [_P, _P]),
@@ -118,6 +122,10 @@ _SIGS = {
     "capgen_debug_adam": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P,
                                     C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                     C.POINTER(_P), _P]),
+    "capgen_debug_adam_scaled": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P,
+                                           _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                           C.POINTER(_P), _P, _P]),
+    "capgen_debug_grad_norm": (C.c_int, [_P, C.c_int64, C.c_float, C.c_int, _P, C.c_int, _P, _P]),
     "capgen_debug_to_bf16": (C.c_int, [_P, _P, C.c_int64, _P]),
     "capgen_debug_arena_checksum": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_uint64), _P]),
     "capgen_debug_argmax_softmax": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int,

@@ -40,6 +40,7 @@ class Engine:
         _lib.check(self.lib.capgen_create(C.byref(self._c), idx, C.byref(h)))
         self.h = h
         self.training = True
+        self.grad_clip = None  # the max_norm set_grad_clip last set (None: clipping off)
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
 
     def close(self):
@@ -65,6 +66,56 @@ class Engine:
 
     def set_graph(self, enable: bool):
         _lib.check(self.lib.capgen_set_graph(self.h, int(enable)))
+
+    # ---- run-time optimizer control --------------------------------------------------------
+    def set_lr(self, lr: float):
+        """The Adam learning rate of every update issued from now on (finite, >= 0; capgen_set_lr): a
+        replayed step graph reads the new value, nothing is re-captured."""
+        _lib.check(self.lib.capgen_set_lr(self.h, float(lr)))
+
+    @property
+    def lr(self) -> float:
+        """The learning rate last set (cfg.learning_rate until the first set_lr), as the f32 the engine uses."""
+        v = C.c_float(0)
+        _lib.check(self.lib.capgen_get_lr(self.h, C.byref(v)))
+        return v.value
+
+    def set_grad_clip(self, max_norm: float | None):
+        """Clip every update's gradients to the global L2 norm `max_norm`, as
+        torch.nn.utils.clip_grad_norm_ does (capgen_set_grad_clip): None or 0 = off (default), a finite
+        value > 0 clips, float('inf') only measures the norm (see grad_norm)."""
+        _lib.check(self.lib.capgen_set_grad_clip(self.h, 0.0 if max_norm is None else float(max_norm)))
+        self.grad_clip = None if not max_norm else float(max_norm)
+
+    def grad_norm(self) -> float:
+        """The global gradient L2 norm, before clipping, of the most recent update that ran with clipping
+        or measuring on (synchronous; raises if there was none)."""
+        v = C.c_float(0)
+        _lib.check(self.lib.capgen_last_grad_norm(self.h, C.byref(v)))
+        return v.value
+
+    def adam_step_count(self) -> int:
+        """The number of Adam updates so far (the optimizer's step counter t; follows set_adam_state).
+        Synchronous: the trainers read it once and count their own steps from there."""
+        torch.cuda.current_stream(self.device).synchronize()
+        step = C.c_int64(0)
+        _lib.check(self.lib.capgen_get_adam_state(self.h, C.byref(step), None, None, self.arena_elems))
+        return step.value
+
+    def set_adam_state(self, step: int, exp_avg: np.ndarray | None = None, exp_avg_sq: np.ndarray | None = None):
+        """Restore the optimizer (capgen_set_adam_state): the step counter and the two moment arenas
+        (f32, the parameter arena's layout; None = zeros).  A trainer created afterwards continues its
+        lr_schedule from `step`."""
+        def arr(a):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            assert a.size == self.arena_elems
+            return a, a.ctypes.data_as(C.c_void_p)
+        torch.cuda.current_stream(self.device).synchronize()
+        m, mp = arr(exp_avg)
+        v, vp = arr(exp_avg_sq)
+        _lib.check(self.lib.capgen_set_adam_state(self.h, int(step), mp, vp, self.arena_elems))
 
     def _arena_to_host(self, fn) -> np.ndarray:
         buf = np.empty(self.arena_elems, dtype=np.float32)

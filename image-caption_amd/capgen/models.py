@@ -13,6 +13,7 @@ import torch
 
 from .config import CapgenConfig
 from .model import PolicyNetwork, Transformer
+from .schedule import ScheduledSteps
 from .staging import HostBatchStager
 from .utils import decode_captions, leave_one_out_baseline, load_word_to_idx, rollout_captions, sequence_logprob
 
@@ -66,6 +67,10 @@ class MODEL_init:
     def decode_captions(self, caption_vector):
         return decode_captions(caption_vector, self.idx_to_word)
 
+    def set_schedule(self, lr_schedule=None, grad_clip=None):
+        """Replace the constructor's lr_schedule / grad_clip (capgen.train.train forwards its own here)."""
+        self._sched = ScheduledSteps(self.model.engine, lr_schedule, grad_clip)
+
     def save(self, path):
         torch.save(self.model.state_dict(), path)
 
@@ -76,13 +81,19 @@ class MODEL_init:
 
 
 class TRANSFORMER(MODEL_init):
+    """grad_clip: clip every update's gradients to this global L2 norm (torch's clip_grad_norm_;
+    float('inf') only measures, engine.grad_norm()); lr_schedule: a callable t -> learning rate
+    (capgen.schedule), applied before each train step with t the Adam step number of that update.
+    None (default) for both: the engine is never told anything."""
+
     def __init__(self, config: CapgenConfig | None = None, word_to_idx=None, word_to_idx_path=None,
-                 device="cuda:0", state_dict=None):
+                 device="cuda:0", state_dict=None, grad_clip=None, lr_schedule=None):
         super().__init__(word_to_idx, word_to_idx_path)
         cfg = (config or CapgenConfig()).replace(num_vocab=self.num_vocab)
         self.config = cfg
         self.device = torch.device(device)
         self.model = Transformer.from_config(cfg, self.device, state_dict=state_dict)
+        self._sched = ScheduledSteps(self.model.engine, lr_schedule, grad_clip)
         self._stage = {}
         self._host_stager = None
 
@@ -100,6 +111,7 @@ class TRANSFORMER(MODEL_init):
         Host (CPU / numpy) batches -- what main.py's DataLoader yields -- go through pinned,
         double-buffered staging with the copy on a side stream, overlapped with the previous
         step (capgen.staging.HostBatchStager); device tensors are staged by a D2D copy."""
+        self._sched.before_step()
         if not _on_device(batch_features):
             st = self._host_stager
             if st is None or not st.fits(batch_features, batch_positions, batch_captions):
@@ -117,6 +129,7 @@ class TRANSFORMER(MODEL_init):
     def train_step_resident(self, store, img_idx, captions):
         """train_step over an HBM-resident split (capgen.data.DeviceFeatureStore / ResidentBatches):
         the batch names its images; nothing is copied from the host."""
+        self._sched.before_step()
         self.model.engine.train_step_indexed(store.features, store.positions, img_idx, captions)
 
     def compute_loss(self, object_features, position_features, target_caption):
@@ -141,7 +154,8 @@ class SelfCriticNetwork(MODEL_init):
 
     def __init__(self, config: CapgenConfig | None = None, word_to_idx=None, word_to_idx_path=None,
                  device="cuda:0", state_dict=None, structure_loss_weight=0.5, cider_reward_weight=1.0,
-                 bleu_reward_weight=1.0, entropy_reward_weight=1.0, self_cider_reward_weight=1.0, df="corpus"):
+                 bleu_reward_weight=1.0, entropy_reward_weight=1.0, self_cider_reward_weight=1.0, df="corpus",
+                 grad_clip=None, lr_schedule=None):
         super().__init__(word_to_idx, word_to_idx_path)
         from .scst import RewardScorer
         cfg = (config or CapgenConfig()).replace(num_vocab=self.num_vocab)
@@ -149,6 +163,7 @@ class SelfCriticNetwork(MODEL_init):
         self.device = torch.device(device)
         # PolicyNetwork (model_RL.py): generate_caption then decodes with LogSoftmax scoring
         self.model = PolicyNetwork.from_config(cfg, self.device, state_dict=state_dict)
+        self._sched = ScheduledSteps(self.model.engine, lr_schedule, grad_clip)  # (as TRANSFORMER's)
         if isinstance(df, str) and df == "corpus":
             import warnings
             warnings.warn("capgen SelfCriticNetwork: CIDEr-D document frequencies from the scored references "
@@ -170,6 +185,7 @@ class SelfCriticNetwork(MODEL_init):
 
     def train_step(self, batch_features, batch_positions, batch_captions):
         """models.py:179-195: forward, sample, reward, loss.backward(), Adam step."""
+        self._sched.before_step()
         self._step(batch_features, batch_positions, batch_captions, train=True)
 
     def compute_loss(self, object_features, position_features, target_caption):
@@ -200,7 +216,8 @@ class RolloutSelfCritic(MODEL_init):
 
     def __init__(self, config: CapgenConfig | None = None, word_to_idx=None, word_to_idx_path=None,
                  device="cuda:0", state_dict=None, n_samples=5, temperature=1.0, top_k=0, baseline="greedy",
-                 cider_reward_weight=1.0, bleu_reward_weight=0.0, df="corpus", reward_fn=None, seed=None):
+                 cider_reward_weight=1.0, bleu_reward_weight=0.0, df="corpus", reward_fn=None, seed=None,
+                 grad_clip=None, lr_schedule=None):
         super().__init__(word_to_idx, word_to_idx_path)
         from .scst import RewardScorer
         if baseline not in ("greedy", "mean"):
@@ -211,6 +228,7 @@ class RolloutSelfCritic(MODEL_init):
         self.config = cfg
         self.device = torch.device(device)
         self.model = PolicyNetwork.from_config(cfg, self.device, state_dict=state_dict)
+        self._sched = ScheduledSteps(self.model.engine, lr_schedule, grad_clip)  # (as TRANSFORMER's)
         self.n_samples, self.temperature, self.top_k = int(n_samples), float(temperature), int(top_k)
         self.baseline, self.reward_fn, self.seed = baseline, reward_fn, seed
         self.steps = 0
@@ -256,6 +274,7 @@ class RolloutSelfCritic(MODEL_init):
         return loss, r, base
 
     def train_step(self, batch_features, batch_positions, batch_captions):
+        self._sched.before_step()
         self._step(batch_features, batch_positions, batch_captions, train=True)
 
     def compute_loss(self, object_features, position_features, target_caption):

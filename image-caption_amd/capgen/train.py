@@ -33,9 +33,18 @@ def _gather(store, idx):
 
 def train(model, train_split, valid_split, num_epoch, batch_size, output_path, target_dir=None,
           eval_every=100, sample_every=2500, write_log=("loss",), evaluate=None, log=print,
-          device="cuda:0", feature_dtype=torch.bfloat16, seed=0):
+          device="cuda:0", feature_dtype=torch.bfloat16, seed=0, grad_clip=None, lr_schedule=None):
     """train_split / valid_split: dicts as returned by capgen.data.load_split (features,
-    positions, captions, image_idxs).  Returns the per-epoch score dicts."""
+    positions, captions, image_idxs).  Returns the per-epoch score dicts.
+
+    grad_clip / lr_schedule (both None by default: nothing changes): handed to the model
+    (`model.set_schedule`, the trainers' constructor arguments of the same names).  With clipping or
+    measuring on and "grad_norm" in write_log, the step log also carries the last update's global
+    gradient norm (before clipping)."""
+    if grad_clip is not None or lr_schedule is not None:
+        model.set_schedule(lr_schedule=lr_schedule, grad_clip=grad_clip)
+    log_norm = "grad_norm" in write_log
+    write_log = tuple(k for k in write_log if k != "grad_norm")  # (not a compute_loss key)
     model_dir = os.path.join(output_path, "model")
     os.makedirs(model_dir, exist_ok=True)
     target_dir = target_dir or os.path.join(output_path, "valid")
@@ -66,8 +75,12 @@ def train(model, train_split, valid_split, num_epoch, batch_size, output_path, t
             if (i + 1) % eval_every == 0:
                 tl = loss_of("train", *eval_batches["train"])
                 vl = loss_of("valid", *eval_batches["valid"])
-                log({"step": step, **{k: {"train": tl[k].mean().item(), "valid": vl[k].mean().item()}
-                                      for k in write_log}})
+                entry = {"step": step, **{k: {"train": tl[k].mean().item(), "valid": vl[k].mean().item()}
+                                          for k in write_log}}
+                eng = getattr(getattr(model, "model", None), "engine", None)
+                if log_norm and getattr(eng, "grad_clip", None):
+                    entry["grad_norm"] = eng.grad_norm()
+                log(entry)
             if (i + 1) % sample_every == 0:
                 f, p = _gather(stores["train"], idx[:1])
                 sample, _ = model.generate_caption(object_features=f, position_features=p)

@@ -313,6 +313,45 @@ struct capgen_engine {
   float* pe = nullptr;  // [max_length-1, dd] f32 sinusoid table
   int64_t* step = nullptr;
   float* adam_scal = nullptr;
+  // run-time optimizer control (capgen_set_lr / capgen_set_grad_clip).  opt: device words {lr, max_norm,
+  // norm, coef} -- the Adam prep reads the learning rate, the norm finish reads max_norm and writes
+  // {norm, coef}, the clipped Adam reads coef -- so a captured step sees new values without re-capture.
+  // opt_host: the pinned staging words {lr, max_norm} of the setters' ordered async copies on es;
+  // ev_opt: recorded after such a copy (the next setter waits for it before it overwrites the staging
+  // word, and the bucket stream, which runs the Adam prep, waits for it on the device)
+  float* opt = nullptr;
+  float* opt_host = nullptr;
+  hipEvent_t ev_opt = nullptr;
+  float lr_cur = 0.f;
+  float clip_cur = 0.f;  // 0: clipping off (the default schedule); > 0 clips, +inf measures only
+  bool clip_on() const { return clip_cur != 0.f; }
+  bool norm_valid = false;  // opt[2] holds the norm of an update issued with clip_on()
+  // the norm's partial sums: gn_part[gn_slots_cap] doubles, one slot per sum-of-squares workgroup, filled
+  // in issue order within a step (gn_slots: used so far), and the step's total (all-reduced under DP)
+  double* gn_part = nullptr;
+  double* gn_sum = nullptr;
+  int gn_slots_cap = 0, gn_slots = 0;
+  struct DeferredAdam {
+    int64_t off, n;
+    int grid_cap;
+  };
+  std::vector<DeferredAdam> gn_deferred;  // buckets whose Adam waits for the step's clip coefficient
+  // Adam grid of the deferred buckets (CAPGEN_CLIP_ADAM_GRID; 0: the bucket's own cap).  They sit on the
+  // step's tail with nothing left to run beside, so they take the whole chip: 2.944 vs 2.975 ms per C2
+  // step with 2048 vs 256 workgroups, 1024 and 4096 level with 2048 (2.692 with clipping off;
+  // profiles/r09_gradclip.txt)
+  int clip_adam_grid = knob(Knob::ClipAdamGrid);
+  void set_opt_word(int idx, float v) {
+    // the previous copy may still be queued: it must read the old value (as capgen_dp_set_global_count)
+    CAPGEN_HIP(hipEventSynchronize(ev_opt));
+    opt_host[idx] = v;
+    if (hz::active()) hz::op(es, "opt_copy", {hz::wr(opt + idx, 4)});
+    CAPGEN_HIP(hipMemcpyAsync(opt + idx, opt_host + idx, sizeof(float), hipMemcpyHostToDevice, es));
+    // es follows every step issued so far (leave / the direct step's hand-back), so the copy lands after
+    // their reads; the steps issued from now on read the words on es or on ec
+    hz::record(ev_opt, es);
+    if (ec != es) hz::wait(ec, ev_opt);
+  }
   uint64_t* seed = nullptr;
   float* scalars = nullptr;  // internal loss
   // striped partial sums for the small accumulated gradients (LayerNorm gamma/beta, biases):
@@ -1199,7 +1238,7 @@ struct capgen_engine {
   }
 
   // Adam over arena ranges; ranges are 64-element aligned so the bf16 shadow slices line up
-  void adam_range(int64_t off, int64_t n, hipStream_t s, int grid_cap = 0) {
+  void adam_range(int64_t off, int64_t n, hipStream_t s, int grid_cap = 0, const float* gscale = nullptr) {
     ++wver;  // (the embedding table has no shadow: its bf16 decode copy follows the version too)
     const int64_t ns = shadow ? std::max<int64_t>(0, std::min(n, L.n_dense - off)) : 0;
     // the fronts' tiled weights in this range: written by the Adam kernel itself (else re-tiled after)
@@ -1217,7 +1256,7 @@ struct capgen_engine {
         at.dst[at.n++] = wtile + kv.second.first;
       }
     adam_update(params + off, grads + off, am + off, av + off, (size_t)n, cfg.beta1, cfg.beta2, cfg.eps, adam_scal,
-                ns > 0 ? shadow + off : nullptr, (size_t)ns, s, grid_cap, fused_tiles ? at : AdamTiles{});
+                ns > 0 ? shadow + off : nullptr, (size_t)ns, s, grid_cap, fused_tiles ? at : AdamTiles{}, gscale);
     if (ns > 0) retile(off, ns, s, /*trans_only=*/fused_tiles);  // (the transposed ones: always a launch)
   }
   // Adam grid of the step's last buckets (embedding, encoder LN/biases), which sit between the
@@ -1244,12 +1283,26 @@ struct capgen_engine {
     else dep(es2, ec, ev_b2);
     bucket_update(off, n);
   }
-  // the bucket's all-reduce (DP) + Adam on the bucket stream (its producers already waited for)
+  // the bucket's all-reduce (DP) + Adam on the bucket stream (its producers already waited for).
+  // With clipping on (capgen_set_grad_clip) the bucket's sum of squares follows its reduction and its
+  // Adam is deferred to clip_tail, after the step's last bucket: the norm is known only then.
   void bucket_update(int64_t off, int64_t n, int grid_cap = 0) {
     ++wver;
     zbuckets.push_back({off, n});
+    bucket_reduce(off, n);
+    if (clip_on()) {
+      gn_deferred.push_back({off, n, grid_cap});
+      return;
+    }
+    bucket_adam(off, n, grid_cap, nullptr);
+  }
+  // sharded update (ZeRO-1); buckets are 64-element aligned
+  bool bucket_sharded(int64_t n) const { return zsharded() && n % (4 * zworld()) == 0; }
+  void bucket_reduce(int64_t off, int64_t n) {
     const int zw = zworld();
-    if (zsharded() && n % (4 * zw) == 0) {  // sharded update (ZeRO-1); buckets are 64-element aligned
+    const bool sharded = bucket_sharded(n);
+    int64_t noff = off, nn = n;  // what this rank adds to the step's gradient norm
+    if (sharded) {
       const int64_t c = n / zw, o = off + (int64_t)zrank() * c;
       if (zw > 1) moments_sharded = true;  // this rank's moments are current in its chunks only
       if (comm && zw > 1) grads_sharded = true;  // the gradient arena holds reduce-scattered chunks
@@ -1257,10 +1310,27 @@ struct capgen_engine {
       if (comm) {
         nccl_op(ec, "reduce_scatter", grads + off, n * 4);
         NCCL_CHECK(ncclReduceScatter(grads + off, grads + o, (size_t)c, ncclFloat, ncclSum, comm, ec));
+        noff = o, nn = c;  // the ranks' chunk sums are all-reduced in clip_tail
       }
+      // (capgen_dp_debug_shard: no collectives, every emulated rank holds the full gradients -- the
+      // norm over the whole bucket gives each of them the same coefficient)
+    } else if (comm) {
+      nccl_op(ec, "allreduce(bucket)", grads + off, n * 4);
+      NCCL_CHECK(ncclAllReduce(grads + off, grads + off, (size_t)n, ncclFloat, ncclSum, comm, ec));
+    }
+    if (!clip_on()) return;
+    // a bucket every rank holds whole (all-reduced): clip_tail's all-reduce of the sum would count it
+    // `world` times, so rank 0 alone adds it
+    if (!sharded && comm && world > 1 && rank != 0) return;
+    gn_slots += grad_sumsq(grads + noff, (size_t)nn, gn_part + gn_slots, gn_slots_cap - gn_slots, ec);
+  }
+  void bucket_adam(int64_t off, int64_t n, int grid_cap, const float* gscale) {
+    if (bucket_sharded(n)) {
+      const int zw = zworld();
+      const int64_t c = n / zw, o = off + (int64_t)zrank() * c;
       const int64_t ns = shadow ? std::max<int64_t>(0, std::min(n, L.n_dense - off)) : 0;
       adam_update(params + o, grads + o, am + o, av + o, (size_t)c, cfg.beta1, cfg.beta2, cfg.eps, adam_scal, nullptr, 0,
-                  ec, grid_cap);
+                  ec, grid_cap, AdamTiles{}, gscale);
       // in place: every rank's updated chunk -> params + off (sendbuff = recvbuff + rank * c)
       if (comm) {
         nccl_op(ec, "all_gather", params + off, n * 4);
@@ -1270,11 +1340,24 @@ struct capgen_engine {
       if (ns > 0) retile(off, ns, ec);
       return;
     }
+    adam_range(off, n, ec, grid_cap, gscale);
+  }
+  // the clipped step's tail on the bucket stream, after its last bucket: the slots' sum (all-reduced as
+  // one double under DP: every rank then derives the same coefficient), {norm, coef}, then every
+  // deferred bucket's Adam with its gradients scaled by coef, in issue order.  Every slot read here was
+  // written in this step, so a graph replay needs nothing re-zeroed.
+  void clip_tail() {
+    grad_norm_finish(gn_part, gn_slots, gn_sum, opt + 1, 0.f, opt + 2, comm ? 1 : 3, ec);
     if (comm) {
-        nccl_op(ec, "allreduce(bucket)", grads + off, n * 4);
-        NCCL_CHECK(ncclAllReduce(grads + off, grads + off, (size_t)n, ncclFloat, ncclSum, comm, ec));
-      }
-    adam_range(off, n, ec, grid_cap);
+      nccl_op(ec, "allreduce(gnorm)", gn_sum, 8);
+      NCCL_CHECK(ncclAllReduce(gn_sum, gn_sum, 1, ncclDouble, ncclSum, comm, ec));
+      grad_norm_finish(nullptr, 0, gn_sum, opt + 1, 0.f, opt + 2, 2, ec);
+    }
+    for (const DeferredAdam& d : gn_deferred)
+      bucket_adam(d.off, d.n, clip_adam_grid > 0 ? clip_adam_grid : d.grid_cap, opt + 3);
+    gn_deferred.clear();
+    gn_slots = 0;
+    norm_valid = true;
   }
   // once: the step's buckets cover the arena exactly (each element updated by exactly one bucket)
   void check_buckets() {
@@ -1357,8 +1440,10 @@ struct capgen_engine {
       // through the buckets' events)
       hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
       CAPGEN_HIP(hipStreamIsCapturing(s, &cst));
-      adam_prepare(step, cfg.lr, cfg.beta1, cfg.beta2, adam_scal, cst == hipStreamCaptureStatusNone ? ec : s);
+      adam_prepare(step, opt, cfg.beta1, cfg.beta2, adam_scal, cst == hipStreamCaptureStatusNone ? ec : s);
       zbuckets.clear();
+      gn_deferred.clear();
+      gn_slots = 0;
     }
 
     // classifier: dlogits are unscaled (softmax - onehot); grad_scale folds 1/count (+focal).  The
@@ -1470,6 +1555,7 @@ struct capgen_engine {
     if (bstep) {
       bucket_update(0, L.enc[0].Wqkv, tail_grid);                   // feature/position embedding
       bucket_update(L.enc_lng, L.dec_lng - L.enc_lng, tail_grid);   // encoder LN / biases
+      if (clip_on()) clip_tail();
     }
     join(s);
     if (bstep) {
@@ -1487,9 +1573,18 @@ struct capgen_engine {
 
   void adam(hipStream_t s) {
     ++wver;
-    adam_prepare(step, cfg.lr, cfg.beta1, cfg.beta2, adam_scal, s);
+    adam_prepare(step, opt, cfg.beta1, cfg.beta2, adam_scal, s);
+    // clipping on: the norm of the whole arena (the gradients are whole and, under DP, already
+    // all-reduced on every rank: no collective), then Adam with the scale
+    const float* gscale = nullptr;
+    if (clip_on()) {
+      const int slots = grad_sumsq(grads, (size_t)L.total, gn_part, gn_slots_cap, s);
+      grad_norm_finish(gn_part, slots, nullptr, opt + 1, 0.f, opt + 2, 3, s);
+      gscale = opt + 3;
+      norm_valid = true;
+    }
     adam_update(params, grads, am, av, (size_t)L.total, cfg.beta1, cfg.beta2, cfg.eps, adam_scal, shadow,
-                shadow ? (size_t)L.n_dense : 0, s);
+                shadow ? (size_t)L.n_dense : 0, s, 0, AdamTiles{}, gscale);
     if (shadow) retile(0, L.n_dense, s);
   }
 
@@ -2034,6 +2129,10 @@ struct capgen_engine {
                     (void*)adam_scal, (void*)seed, (void*)scalars, (void*)gstripe, ws, gws, (void*)stamp_ring})
       if (p) (void)hipFree(p);
     if (count_host) (void)hipHostFree(count_host);
+    if (opt_host) (void)hipHostFree(opt_host);
+    for (void* p : {(void*)opt, (void*)gn_part, (void*)gn_sum})
+      if (p) (void)hipFree(p);
+    if (ev_opt) (void)hipEventDestroy(ev_opt);
     if (dp_chk) (void)hipFree(dp_chk);
     if (ev_in) (void)hipEventDestroy(ev_in);
     if (ev_out) (void)hipEventDestroy(ev_out);
@@ -2180,6 +2279,16 @@ int capgen_create(const capgen_config* cfg, int device, capgen_t** out) {
     CAPGEN_HIP(hipMalloc(&h->step, 64));
     CAPGEN_HIP(hipMemset(h->step, 0, 64));
     CAPGEN_HIP(hipMalloc(&h->adam_scal, 64));
+    CAPGEN_HIP(hipMalloc(&h->opt, 64));
+    CAPGEN_HIP(hipMemset(h->opt, 0, 64));
+    h->lr_cur = cfg->lr;
+    CAPGEN_HIP(hipMemcpy(h->opt, &h->lr_cur, sizeof(float), hipMemcpyHostToDevice));
+    CAPGEN_HIP(hipHostMalloc(&h->opt_host, 64, hipHostMallocDefault));
+    CAPGEN_HIP(hipEventCreateWithFlags(&h->ev_opt, hipEventDisableTiming));
+    // one slot per sum-of-squares workgroup: at most 256 per bucket, one bucket per block plus the fixed ones
+    h->gn_slots_cap = 256 * (h->L.Le + h->L.Ld + 16);
+    CAPGEN_HIP(hipMalloc(&h->gn_part, (size_t)h->gn_slots_cap * sizeof(double)));
+    CAPGEN_HIP(hipMalloc(&h->gn_sum, 64));
     CAPGEN_HIP(hipMalloc(&h->seed, 64));
     uint64_t sd = cfg->seed;
     CAPGEN_HIP(hipMemcpy(h->seed, &sd, 8, hipMemcpyHostToDevice));
@@ -2296,6 +2405,49 @@ int capgen_set_graph(capgen_t* h, int enable) {
     require(h != nullptr, "null engine handle");
     h->graph_on = enable != 0;
     if (!h->graph_on) h->drop_graph();
+  });
+}
+
+int capgen_set_lr(capgen_t* h, float lr) {
+  return guarded([&] {
+    set_device(h);
+    require(std::isfinite(lr) && lr >= 0.f, "set_lr: the learning rate must be finite and >= 0");
+    h->set_opt_word(0, lr);
+    h->lr_cur = lr;
+  });
+}
+
+int capgen_get_lr(capgen_t* h, float* lr) {
+  return guarded([&] {
+    require(h != nullptr && lr != nullptr, "get_lr: null argument");
+    *lr = h->lr_cur;
+  });
+}
+
+int capgen_set_grad_clip(capgen_t* h, float max_norm) {
+  return guarded([&] {
+    set_device(h);
+    require(max_norm >= 0.f, "set_grad_clip: max_norm must be 0 (off), > 0 or +inf (measure only)");  // (NaN fails too)
+    const bool on = max_norm != 0.f;
+    // the whole-step graph holds the schedule (norm pass, deferred Adam); the forward graph does not
+    if (on != h->clip_on() && h->gexec) {
+      (void)hipGraphExecDestroy(h->gexec);
+      h->gexec = nullptr;
+    }
+    if (on) h->set_opt_word(1, max_norm);
+    h->clip_cur = max_norm;
+  });
+}
+
+int capgen_last_grad_norm(capgen_t* h, float* host_out) {
+  return guarded([&] {
+    set_device(h);
+    require(host_out != nullptr, "last_grad_norm: null output");
+    require(h->norm_valid, "last_grad_norm: no update has run with clipping or measuring enabled "
+                           "(capgen_set_grad_clip)");
+    hz::host_sync(h->es);
+    hz::host_sync(h->ec);
+    CAPGEN_HIP(hipMemcpy(host_out, h->opt + 2, sizeof(float), hipMemcpyDeviceToHost));
   });
 }
 
@@ -2764,6 +2916,39 @@ int capgen_debug_adam(float* p, const float* g, float* m, float* v, int64_t n, f
     adam_prepare(step, lr, b1, b2, scal, s);
     adam_update(p, g, m, v, (size_t)n, b1, b2, eps, scal, reinterpret_cast<bf16*>(shadow), (size_t)n_shadow, s,
                 grid_cap, tiles);
+  });
+}
+
+int capgen_debug_adam_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
+                             float eps, int64_t* step, float* scal, void* shadow, int64_t n_shadow, int grid_cap,
+                             int n_tiles, const int64_t* tile_off, const int64_t* tile_len, void* const* tile_dst,
+                             const float* gscale, void* stream) {
+  return guarded([&] {
+    const hipStream_t s = (hipStream_t)stream;
+    require(gscale != nullptr, "debug_adam_scaled: null gscale");
+    require(n >= 0 && n_shadow >= 0 && n_shadow <= n, "debug_adam_scaled: 0 <= n_shadow <= n");
+    require(n % 4 == 0 && n_shadow % 4 == 0, "debug_adam_scaled: n and n_shadow must be multiples of 4");
+    require(n_tiles >= 0 && n_tiles <= AdamTiles::kMax, "debug_adam_scaled: at most AdamTiles::kMax tiled ranges");
+    AdamTiles tiles;
+    tiles.n = n_tiles;
+    for (int t = 0; t < n_tiles; ++t)
+      tiles.off[t] = tile_off[t], tiles.len[t] = tile_len[t], tiles.dst[t] = reinterpret_cast<bf16*>(tile_dst[t]);
+    adam_prepare(step, lr, b1, b2, scal, s);
+    adam_update(p, g, m, v, (size_t)n, b1, b2, eps, scal, reinterpret_cast<bf16*>(shadow), (size_t)n_shadow, s,
+                grid_cap, tiles, gscale);
+  });
+}
+
+int capgen_debug_grad_norm(const float* g, int64_t n, float max_norm, int grid_cap, double* partials, int cap,
+                           float* out2, void* stream) {
+  return guarded([&] {
+    const hipStream_t s = (hipStream_t)stream;
+    require(g != nullptr && partials != nullptr && out2 != nullptr, "debug_grad_norm: null argument");
+    require(n >= 0 && n % 4 == 0, "debug_grad_norm: n must be a non-negative multiple of 4");
+    require(max_norm >= 0.f, "debug_grad_norm: max_norm must be >= 0 (+inf: measure only)");
+    require(cap >= grad_sumsq_grid((size_t)n, grid_cap), "debug_grad_norm: the partials buffer is too small");
+    const int slots = grad_sumsq(g, (size_t)n, partials, cap, s, grid_cap);
+    grad_norm_finish(partials, slots, nullptr, nullptr, max_norm, out2, 3, s);
   });
 }
 

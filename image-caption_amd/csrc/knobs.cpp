@@ -54,6 +54,7 @@ constexpr KnobDef kDefs[] = {
     {Knob::EventFence, "EVENT_FENCE", 1, false},      // 1 no system fence, 2 device release, 0 HIP default
     {Knob::DeferLoss, "DEFER_LOSS", 1, false},        // train step's loss mean on es2 (0: on the critical stream)
     {Knob::FrontJoin, "FRONT_JOIN", 99, false},       // forward joins the decoder front before encoder block N (> Le: before the decoder)
+    {Knob::ClipAdamGrid, "CLIP_ADAM_GRID", 2048, false},  // Adam workgroups of the clipped step's deferred buckets (0: the bucket's own cap)
     {Knob::Autotune, "AUTOTUNE", 1, false},           // time GEMM shapes the tune table lacks
     {Knob::AutotuneLog, "AUTOTUNE_LOG", 0, false},    // print tuning decisions
     // debug build only

@@ -97,9 +97,23 @@ struct AdamTiles {
   int64_t len[kMax] = {};
   bf16* dst[kMax] = {};
 };
+// gscale (optional, one device float): every gradient is multiplied by *gscale before both moment updates
 void adam_update(float* p, const float* g, float* m, float* v, size_t n, float b1, float b2, float eps,
                  const float* scal, bf16* shadow, size_t n_shadow, hipStream_t s, int grid_cap = 0,
-                 const AdamTiles& tiles = AdamTiles{});
+                 const AdamTiles& tiles = AdamTiles{}, const float* gscale = nullptr);
+// the learning rate read from a device word (the same formula: an unchanged rate gives the same bits)
+void adam_prepare(int64_t* step, const float* lr, float b1, float b2, float* scal, hipStream_t s);
+// Global gradient norm (torch.nn.utils.clip_grad_norm_).  grad_sumsq: the sum of squares of g[0, n)
+// (16-byte aligned, n % 4 == 0) in double, one double per workgroup into partials[0, grid) by plain
+// stores (no atomics: the value depends on n and the grid only); returns grid = grad_sumsq_grid(n,
+// grid_cap) <= slots_cap (grid_cap 0: one workgroup per CU).  grad_norm_finish (one workgroup): phase & 1
+// adds partials[0, n_slots) in slot order into *sum (double; null with phase 3: not stored); phase & 2
+// writes out2 = {norm = (float)sqrt(*sum), coef = (float)min(1, max_norm / (norm + 1e-6))}, max_norm =
+// *max_norm_ptr if given, else max_norm_val (+inf: coef = 1 exactly).  Definitions: ops.hip.
+int grad_sumsq_grid(size_t n, int grid_cap = 0);
+int grad_sumsq(const float* g, size_t n, double* partials, int slots_cap, hipStream_t s, int grid_cap = 0);
+void grad_norm_finish(const double* partials, int n_slots, double* sum, const float* max_norm_ptr,
+                      float max_norm_val, float* out2, int phase, hipStream_t s);
 void to_bf16(const float* src, bf16* dst, size_t n, hipStream_t s);
 // exact, order-independent checksum of an f32 arena (sum of bit patterns x (2 i + 1) mod 2^64); synchronous
 uint64_t arena_checksum(const float* p, size_t n, hipStream_t s);

@@ -825,7 +825,21 @@ void adam_prepare(int64_t* step, float lr, float b1, float b2, float* scal, hipS
   adam_prep_kernel<<<1, 1, 0, s>>>(step, lr, b1, b2, scal);
   CAPGEN_HIP(hipGetLastError());
 }
-
+// the same with the learning rate read from a device word (capgen_set_lr: a captured step sees a new
+// value without re-capture); the same formula, so an unchanged rate gives the same bits
+__global__ void adam_prep_dev_kernel(int64_t* step, const float* lr, float b1, float b2, float* scal) {
+  const int64_t t = ++(*step);
+  const double bc1 = 1.0 - pow((double)b1, (double)t);
+  const double bc2 = 1.0 - pow((double)b2, (double)t);
+  scal[0] = (float)(-(double)*lr / bc1);
+  scal[1] = (float)sqrt(bc2);
+}
+void adam_prepare(int64_t* step, const float* lr, float b1, float b2, float* scal, hipStream_t s) {
+  require(lr != nullptr, "adam_prepare: null learning-rate word");
+  if (hz::active()) hz::op(s, "adam_prepare", {hz::rd(lr, 4), hz::wr(step, 8), hz::wr(scal, 8)});
+  adam_prep_dev_kernel<<<1, 1, 0, s>>>(step, lr, b1, b2, scal);
+  CAPGEN_HIP(hipGetLastError());
+}
 
 // Adam streams 30 B per parameter that nothing else in the step reads (f32 params, grads, moments:
 // 16 B in, 12 B out) beside the critical chain, so (a) those streams use non-temporal loads and
@@ -836,11 +850,19 @@ void adam_prepare(int64_t* step, float lr, float b1, float b2, float* scal, hipS
 // iteration measured 3.1 TB/s, round 4).
 constexpr int ADAM_U = 4;
 typedef float adam_f4 __attribute__((ext_vector_type(4)));  // (the nontemporal builtins take clang vectors)
+// GScale empty: the kernel as it was (the same parameters, the same code).  GScale = const float*: every
+// gradient is multiplied by *gscale (the clip coefficient of grad_norm_finish) once, before both
+// moment updates.
+template <class... GScale>
 __global__ void __launch_bounds__(256) adam_kernel(adam_f4* __restrict__ p, const adam_f4* __restrict__ g,
                                                    adam_f4* __restrict__ m, adam_f4* __restrict__ v, size_t n4,
                                                    float b1, float b2, float eps, const float* __restrict__ scal,
-                                                   bf16* __restrict__ shadow, size_t n_shadow, AdamTiles tiles) {
+                                                   bf16* __restrict__ shadow, size_t n_shadow, AdamTiles tiles,
+                                                   GScale... gscale) {
+  constexpr bool SCALED = sizeof...(GScale) > 0;
   const float neg_step = scal[0], bc2s = scal[1];
+  float gs = 1.f;
+  if constexpr (SCALED) gs = *(gscale, ...);
   const float b1c = 1.f - b1, b2c = 1.f - b2;
   const size_t stride = (size_t)gridDim.x * 256 * ADAM_U;
   for (size_t base = blockIdx.x * (size_t)(256 * ADAM_U) + threadIdx.x; base < n4; base += stride) {
@@ -865,7 +887,9 @@ __global__ void __launch_bounds__(256) adam_kernel(adam_f4* __restrict__ p, cons
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         float pc = pp[u][c], mc = mm[u][c], vc = vv[u][c];
-        adam_one(pc, gg[u][c], mc, vc, b1c, b2, b2c, eps, neg_step, bc2s);
+        float gc = gg[u][c];
+        if constexpr (SCALED) gc *= gs;
+        adam_one(pc, gc, mc, vc, b1c, b2, b2c, eps, neg_step, bc2s);
         pp[u][c] = pc, mm[u][c] = mc, vv[u][c] = vc;
       }
       __builtin_nontemporal_store(pp[u], p + i);
@@ -893,7 +917,7 @@ __global__ void __launch_bounds__(256) adam_kernel(adam_f4* __restrict__ p, cons
 }
 void adam_update(float* p, const float* g, float* m, float* v, size_t n, float b1, float b2, float eps,
                  const float* scal, bf16* shadow, size_t n_shadow, hipStream_t s, int grid_cap,
-                 const AdamTiles& tiles) {
+                 const AdamTiles& tiles, const float* gscale) {
   require(tiles.n >= 0 && tiles.n <= AdamTiles::kMax, "adam: at most kMax tiled ranges");
   for (int t = 0; t < tiles.n; ++t)
     // (the tile formula needs only the element offset from the matrix start; 4-aligned so a thread's
@@ -904,7 +928,7 @@ void adam_update(float* p, const float* g, float* m, float* v, size_t n, float b
   require(n % 4 == 0 && n_shadow % 4 == 0, "adam: arena size must be a multiple of 4");
   if (skip_mask() & 32) return;
   if (hz::active())
-    hz::op(s, "adam", {hz::rd(g, (int64_t)n * 4), hz::rd(scal, 8), hz::wr(p, (int64_t)n * 4), hz::wr(m, (int64_t)n * 4),
+    hz::op(s, "adam", {hz::rd(g, (int64_t)n * 4), hz::rd(scal, 8), hz::rd(gscale, 4), hz::wr(p, (int64_t)n * 4), hz::wr(m, (int64_t)n * 4),
                        hz::wr(v, (int64_t)n * 4), hz::wr(shadow, (int64_t)n_shadow * 2),
                        hz::wr(tiles.n > 0 ? tiles.dst[0] : nullptr, tiles.n > 0 ? tiles.len[0] * 2 : 0),
                        hz::wr(tiles.n > 1 ? tiles.dst[1] : nullptr, tiles.n > 1 ? tiles.len[1] * 2 : 0),
@@ -916,8 +940,117 @@ void adam_update(float* p, const float* g, float* m, float* v, size_t n, float b
   constexpr int cap = 256;
   // grid_cap > 0: the caller's cap (an update on the step's critical path takes the whole chip)
   int grid = (int)std::min<size_t>((n4 + 256 * ADAM_U - 1) / (256 * ADAM_U), (size_t)(grid_cap > 0 ? grid_cap : cap));
-  adam_kernel<<<grid, 256, 0, s>>>((adam_f4*)p, (const adam_f4*)g, (adam_f4*)m, (adam_f4*)v, n4, b1, b2, eps, scal,
-                                   shadow, n_shadow, tiles);
+  if (gscale)
+    adam_kernel<const float*><<<grid, 256, 0, s>>>((adam_f4*)p, (const adam_f4*)g, (adam_f4*)m, (adam_f4*)v, n4, b1, b2,
+                                                   eps, scal, shadow, n_shadow, tiles, gscale);
+  else
+    adam_kernel<><<<grid, 256, 0, s>>>((adam_f4*)p, (const adam_f4*)g, (adam_f4*)m, (adam_f4*)v, n4, b1, b2, eps, scal,
+                                     shadow, n_shadow, tiles);
+  CAPGEN_HIP(hipGetLastError());
+}
+
+// ---- gradient norm (global-norm clipping) ------------------------------------------------
+// Sum of squares of a flat f32 range, accumulated in double: the square of an f32 is exact in
+// double and the kernel is memory-bound (one f64 FMA per 4 bytes loaded), so neither a 1e20 element
+// nor a range of 1e-30s is lost.  Loads as in adam_kernel: 16 B, non-temporal, GNORM_U of them in
+// flight per thread before the first use.  The sum is reduced per wave by shuffle and per workgroup
+// through LDS, and every workgroup writes ONE double into its own slot with a plain store: no
+// float / double atomics, so the value depends on (n, grid) only -- equal on every run and on every
+// data-parallel rank that holds equal gradients (an arrival-ordered sum would let the clip
+// coefficient, and then the parameters, differ in the last bit between ranks).
+constexpr int GNORM_U = 4;
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(const adam_f4* __restrict__ g, size_t n4,
+                                                         double* __restrict__ partials) {
+  __shared__ double sh[4];
+  double acc = 0.0;
+  const size_t stride = (size_t)gridDim.x * 256 * GNORM_U;
+  for (size_t base = blockIdx.x * (size_t)(256 * GNORM_U) + threadIdx.x; base < n4; base += stride) {
+    adam_f4 gg[GNORM_U];
+#pragma unroll
+    for (int u = 0; u < GNORM_U; ++u) {
+      // (a lane past the end re-reads element base: in range, its value is not added)
+      const size_t i = base + (size_t)u * 256 < n4 ? base + (size_t)u * 256 : base;
+      gg[u] = __builtin_nontemporal_load(g + i);
+    }
+#pragma unroll
+    for (int u = 0; u < GNORM_U; ++u) asm volatile("" : "+v"(gg[u]));
+#pragma unroll
+    for (int u = 0; u < GNORM_U; ++u) {
+      if (base + (size_t)u * 256 >= n4) break;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const double x = (double)gg[u][c];
+        acc = fma(x, x, acc);
+      }
+    }
+  }
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+int grad_sumsq_grid(size_t n, int grid_cap) {
+  constexpr int cap = 256;  // one workgroup per CU: the kernel runs beside the critical chain (as adam_update)
+  const size_t n4 = n / 4;
+  return (int)std::min<size_t>((n4 + 256 * GNORM_U - 1) / (256 * GNORM_U), (size_t)(grid_cap > 0 ? grid_cap : cap));
+}
+int grad_sumsq(const float* g, size_t n, double* partials, int slots_cap, hipStream_t s, int grid_cap) {
+  require(n % 4 == 0, "grad_sumsq: the range must be a multiple of 4 elements");
+  require(g != nullptr && ((uintptr_t)g & 15) == 0, "grad_sumsq: the range must be 16-byte aligned");
+  const int grid = grad_sumsq_grid(n, grid_cap);
+  require(partials != nullptr && grid <= slots_cap, "grad_sumsq: the partials buffer is too small");
+  if (grid == 0) return 0;
+  if (hz::active()) hz::op(s, "grad_sumsq", {hz::rd(g, (int64_t)n * 4), hz::wr(partials, (int64_t)grid * 8)});
+  grad_sumsq_kernel<<<grid, 256, 0, s>>>((const adam_f4*)g, n / 4, partials);
+  CAPGEN_HIP(hipGetLastError());
+  return grid;
+}
+
+// One wave: lane l sums the contiguous slots [l k, (l + 1) k), k = ceil(n_slots / 64), in slot order, and
+// lane 0 adds the 64 lane sums in lane order -- the slots left to right, in double, in an association
+// fixed by n_slots alone.  phase & 1: *sum = that total (sum == null: kept in a register); phase & 2:
+// out2 = {norm = (float)sqrt(sum), coef = (float)min(1, max_norm / (norm + 1e-6))}, the coefficient of
+// torch.nn.utils.clip_grad_norm_ (error_if_nonfinite=False; a non-finite norm is passed through as
+// torch does).  Two launches (phase 1, then 2) leave room for an all-reduce of *sum in between.
+__global__ void __launch_bounds__(64) grad_norm_finish_kernel(const double* __restrict__ partials, int n_slots,
+                                                              double* sum, const float* max_norm_ptr,
+                                                              float max_norm_val, float* out2, int phase) {
+  __shared__ double sh[64];
+  double total = 0.0;
+  if (phase & 1) {
+    const int k = (n_slots + 63) / 64;
+    double acc = 0.0;
+    for (int i = threadIdx.x * k; i < min(n_slots, (int)(threadIdx.x + 1) * k); ++i) acc += partials[i];
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int l = 0; l < 64; ++l) total += sh[l];
+      if (sum) *sum = total;
+    }
+  } else if (threadIdx.x == 0) {
+    total = *sum;
+  }
+  if ((phase & 2) && threadIdx.x == 0) {
+    const float max_norm = max_norm_ptr ? *max_norm_ptr : max_norm_val;
+    const float norm = (float)sqrt(total);
+    out2[0] = norm;
+    // torch: clip_coef = max_norm / (total_norm + 1e-6), clamped to at most 1 (max_norm = +inf: exactly 1)
+    const double coef = (double)max_norm / ((double)norm + 1e-6);
+    out2[1] = (float)(coef > 1.0 ? 1.0 : coef);  // (a NaN coefficient stays NaN, as torch.clamp leaves it)
+  }
+}
+void grad_norm_finish(const double* partials, int n_slots, double* sum, const float* max_norm_ptr,
+                      float max_norm_val, float* out2, int phase, hipStream_t s) {
+  require(phase >= 1 && phase <= 3, "grad_norm_finish: phase 1 (slot sum), 2 (norm + coefficient) or 3 (both)");
+  require(n_slots >= 0 && (!(phase & 1) || n_slots == 0 || partials), "grad_norm_finish: null partials");
+  require(phase == 3 || sum, "grad_norm_finish: a split finish needs the sum word");
+  require(!(phase & 2) || out2, "grad_norm_finish: null output");
+  if (hz::active())
+    hz::op(s, "grad_norm_finish",
+           {hz::rd(phase & 1 ? partials : nullptr, (int64_t)n_slots * 8), hz::rd(phase & 1 ? nullptr : sum, 8),
+            hz::wr(phase & 1 ? sum : nullptr, 8), hz::rd(phase & 2 ? max_norm_ptr : nullptr, 4),
+            hz::wr(phase & 2 ? out2 : nullptr, 8)});
+  grad_norm_finish_kernel<<<1, 64, 0, s>>>(partials, n_slots, sum, max_norm_ptr, max_norm_val, out2, phase);
   CAPGEN_HIP(hipGetLastError());
 }
 

@@ -122,6 +122,29 @@ int capgen_adam_step(capgen_t* h, void* stream);
 int capgen_train_step(capgen_t* h, const void* feats, int feats_dtype, const float* pos, const int32_t* caps,
                       int B, int N, int T, float* loss_out, void* stream);
 int capgen_set_graph(capgen_t* h, int enable);
+/* Run-time optimizer control (warm-up / decay schedules, the drop from the cross-entropy rate to the
+ * self-critical one, gradient clipping).  Off by default: without these calls a step's launches, streams,
+ * RCCL call sequence, captured graphs and arithmetic are unchanged.
+ * capgen_set_lr: the Adam learning rate (finite, >= 0; capgen_config.lr until the first call) of every
+ * update issued after the call and of none issued before.  The value lives in a device word written by an
+ * ordered asynchronous copy, so a replayed step graph picks it up without re-capture (graph keys do not
+ * change).  capgen_get_lr: the value last set (host side, no synchronisation).
+ * capgen_set_grad_clip: torch.nn.utils.clip_grad_norm_(parameters, max_norm) (L2, error_if_nonfinite=False)
+ * before every Adam update: 0 = off (default), finite > 0 clips, +inf only measures the norm (the
+ * coefficient is exactly 1); negative or NaN fails.  The norm is the global L2 norm of the step's
+ * gradients -- under data parallel of the summed gradients, one 8-byte all-reduce per step on the bucket
+ * stream -- accumulated in double in a fixed order, so equal gradients give equal coefficients on every
+ * rank and run.  In a train step every bucket's Adam then runs after the step's last bucket
+ * (capgen_train_step, _indexed, _weighted, capgen_rl_finish); capgen_adam_step clips over the whole
+ * arena.  Switching between off and on drops the captured whole-step graph (not the forward graph); a new
+ * value while on is read by the replay.
+ * capgen_last_grad_norm (synchronous): the norm, before clipping, of the most recent update issued with
+ * clipping or measuring on, into the HOST float *host_out; fails if there was none.
+ * Added without a change of CAPGEN_ABI_VERSION: no existing entry changed (backward compatible). */
+int capgen_set_lr(capgen_t* h, float lr);
+int capgen_get_lr(capgen_t* h, float* lr);
+int capgen_set_grad_clip(capgen_t* h, float max_norm);
+int capgen_last_grad_norm(capgen_t* h, float* host_out);
 /* TRANSFORMER.compute_loss (models.py:128-135): forward under no_grad. */
 int capgen_compute_loss(capgen_t* h, const void* feats, int feats_dtype, const float* pos, const int32_t* caps,
                         int B, int N, int T, float* loss_out, void* stream);
@@ -362,6 +385,18 @@ int capgen_debug_adam(float* p, const float* g, float* m, float* v, int64_t n, f
                       float eps, int64_t* step, float* scal, void* shadow, int64_t n_shadow, int grid_cap,
                       int n_tiles, const int64_t* tile_off, const int64_t* tile_len, void* const* tile_dst,
                       void* stream);
+/* capgen_debug_adam with every gradient multiplied by the device float *gscale (required) before both
+ * moment updates: the clipped update.  capgen_debug_grad_norm: the sum-of-squares kernel over g[0, n)
+ * (n % 4 == 0; grid_cap > 0 caps the workgroups) into the device doubles partials[0, cap), one per
+ * workgroup, then the finish kernel: out2 (2 device floats) = {norm = (float)sqrt(sum), coef =
+ * (float)min(1, max_norm / (norm + 1e-6))}; max_norm >= 0, +inf gives coef = 1 exactly.  Fails (1) when
+ * n % 4 != 0, a pointer is null or cap is smaller than the grid. */
+int capgen_debug_adam_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
+                             float eps, int64_t* step, float* scal, void* shadow, int64_t n_shadow, int grid_cap,
+                             int n_tiles, const int64_t* tile_off, const int64_t* tile_len, void* const* tile_dst,
+                             const float* gscale, void* stream);
+int capgen_debug_grad_norm(const float* g, int64_t n, float max_norm, int grid_cap, double* partials, int cap,
+                           float* out2, void* stream);
 int capgen_debug_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 int capgen_debug_arena_checksum(const float* p, int64_t n, uint64_t* out, void* stream);
 /* Decode selection.  argmax_softmax: ids_out[b * ids_ld + col] (and next_ids[b * next_ld]) = argmax of
