@@ -75,6 +75,8 @@ _SIGS = {
     "capgen_beam": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "capgen_sample": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, _P, _P,
                                 _P]),
+    "capgen_sample_nucleus": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
+                                        C.c_uint64, _P, _P, _P]),
     "capgen_set_rng_seed": (C.c_int, [_P, C.c_uint64]),
     "capgen_debug_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int,
                                     _P, C.c_int64, C.c_int, C.c_int, _P, C.c_float, C.c_int, C.c_int, _P]),
@@ -132,6 +134,9 @@ _SIGS = {
                                               _P]),
     "capgen_debug_sample_softmax": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint32, _P,
                                               C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int, _P]),
+    "capgen_debug_sample_nucleus": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64,
+                                              C.c_uint32, _P, C.c_int64, C.c_int, _P, C.c_int64, _P, C.c_int64,
+                                              C.c_int, _P, _P]),
     "capgen_debug_slab_argmax": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, _P]),
     "capgen_debug_beam_step_topk": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
                                               _P, _P]),

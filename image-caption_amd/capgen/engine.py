@@ -321,9 +321,11 @@ class Engine:
                                         _stream(self.device)))
         return ids
 
-    def sample(self, feats, pos, n_samples=1, temperature=1.0, top_k=0, seed=0, want_logp=True):
+    def sample(self, feats, pos, n_samples=1, temperature=1.0, top_k=0, seed=0, want_logp=True, top_p=1.0):
         """n_samples captions per image drawn from softmax(logits / temperature) over the top_k largest
-        logits (0: the whole vocabulary), KV-cached, one encoder pass (capgen_sample).  Returns
+        logits (0: the whole vocabulary), KV-cached, one encoder pass (capgen_sample_nucleus).  top_p in
+        (0, 1] cuts those candidates to the nucleus: the most likely words up to the one at which their
+        mass reaches top_p, renormalised (1.0: no cut, exactly capgen_sample).  Returns
         (ids int64 [n, B, T+1] laid out as greedy's, logp f32 [n, B, T-1] or None): logp holds each
         token's log-probability under the distribution it was drawn from.  One (seed, inputs,
         weights) gives one result."""
@@ -333,9 +335,9 @@ class Engine:
         rows = max(n, 0) * B
         ids = torch.empty(rows, T + 1, dtype=torch.int64, device=self.device)
         logp = torch.empty(rows, T - 1, dtype=torch.float32, device=self.device) if want_logp else None
-        _lib.check(self.lib.capgen_sample(self.h, _ptr(f), ft, _ptr(p), B, N, n, float(temperature), int(top_k),
-                                          int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(ids), _ptr(logp),
-                                          _stream(self.device)))
+        _lib.check(self.lib.capgen_sample_nucleus(self.h, _ptr(f), ft, _ptr(p), B, N, n, float(temperature),
+                                                  int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                  _ptr(ids), _ptr(logp), _stream(self.device)))
         return ids.view(n, B, T + 1), (logp.view(n, B, T - 1) if want_logp else None)
 
     # ---- SCST (SelfCriticNetwork) -------------------------------------------------------

@@ -119,15 +119,15 @@ class Transformer:
         return self.engine.beam(object_features, position_features, beam_size)
 
     def sample_caption_vector(self, object_features, position_features, n_samples=1, temperature=1.0, top_k=0,
-                              seed=None):
-        """n_samples captions per image drawn from the model's distribution (temperature / top-k
-        sampling; no counterpart in the reference, whose decoding is greedy or beam search only).
+                              seed=None, top_p=1.0):
+        """n_samples captions per image drawn from the model's distribution (temperature / top-k /
+        nucleus top_p sampling; no counterpart in the reference, whose decoding is greedy or beam search only).
         Returns (ids LongTensor [n, B, max_length+1], logp f32 [n, B, max_length-1]).  seed=None draws
         the seed from torch's global CPU generator: torch.manual_seed makes a run reproducible."""
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         return self.engine.sample(object_features, position_features, n_samples=n_samples, temperature=temperature,
-                                  top_k=top_k, seed=seed)
+                                  top_k=top_k, seed=seed, top_p=top_p)
 
     def get_attention_key_pad_mask(self, k, q):
         """model.py:202-209 (host helper; the kernels derive the same mask on device)."""

@@ -52,13 +52,15 @@ class MODEL_init:
         assert isinstance(beam_size, int)
         assert beam_size > 1 or beam_size in [None, 1]
 
-    def sample_captions(self, object_features, position_features, n_samples=1, temperature=1.0, top_k=0, seed=None):
-        """n_samples captions per image drawn from the model's distribution (temperature / top-k
-        sampling): (captions, logprob) -- n lists of B strings and each caption's log-probability
+    def sample_captions(self, object_features, position_features, n_samples=1, temperature=1.0, top_k=0, seed=None,
+                        top_p=1.0):
+        """n_samples captions per image drawn from the model's distribution (temperature / top-k /
+        nucleus top_p sampling): (captions, logprob) -- n lists of B strings and each caption's log-probability
         [n, B] (f32, on the model's device: the sum of its token log-probabilities through <END>)."""
         ids, logp = self.model.sample_caption_vector(object_features=object_features,
                                                      position_features=position_features, n_samples=n_samples,
-                                                     temperature=temperature, top_k=top_k, seed=seed)
+                                                     temperature=temperature, top_k=top_k, seed=seed,
+                                                     top_p=top_p)
         host = ids.cpu().numpy()
         end = -1 if self.end_idx is None else self.end_idx  # (no <END> in the vocabulary: every token counts)
         logprob = sequence_logprob(ids[..., 1:logp.shape[-1] + 1], logp, end)
@@ -208,7 +210,7 @@ class RolloutSelfCritic(MODEL_init):
     ("mean", n_samples >= 2); one engine.train_step_weighted on the n * B sampled captions with the
     advantages as per-caption weights ascends advantage * log p(sample).  The n * B caption rows
     share the B images through img_idx, and the bf16 step keeps the fused classifier + CE.
-    temperature / top_k shape the behaviour policy only: the gradient is taken through the model's
+    temperature / top_k / top_p shape the behaviour policy only: the gradient is taken through the model's
     own log-probabilities.
 
     reward_fn(target_ids [B, L], sample_ids [B, L]) -> [B] (host numpy) replaces the scorer.
@@ -217,7 +219,7 @@ class RolloutSelfCritic(MODEL_init):
     def __init__(self, config: CapgenConfig | None = None, word_to_idx=None, word_to_idx_path=None,
                  device="cuda:0", state_dict=None, n_samples=5, temperature=1.0, top_k=0, baseline="greedy",
                  cider_reward_weight=1.0, bleu_reward_weight=0.0, df="corpus", reward_fn=None, seed=None,
-                 grad_clip=None, lr_schedule=None):
+                 grad_clip=None, lr_schedule=None, top_p=1.0):
         super().__init__(word_to_idx, word_to_idx_path)
         from .scst import RewardScorer
         if baseline not in ("greedy", "mean"):
@@ -230,6 +232,7 @@ class RolloutSelfCritic(MODEL_init):
         self.model = PolicyNetwork.from_config(cfg, self.device, state_dict=state_dict)
         self._sched = ScheduledSteps(self.model.engine, lr_schedule, grad_clip)  # (as TRANSFORMER's)
         self.n_samples, self.temperature, self.top_k = int(n_samples), float(temperature), int(top_k)
+        self.top_p = float(top_p)
         self.baseline, self.reward_fn, self.seed = baseline, reward_fn, seed
         self.steps = 0
         self._stage = {}
@@ -254,7 +257,7 @@ class RolloutSelfCritic(MODEL_init):
         if not (_on_device(batch_features) and _on_device(batch_positions)):
             f, p = self._staged("f", f, f.dtype), self._staged("p", p, torch.float32)
         B = f.shape[0]
-        ids, _ = eng.sample(f, p, n, self.temperature, self.top_k, seed, want_logp=False)
+        ids, _ = eng.sample(f, p, n, self.temperature, self.top_k, seed, want_logp=False, top_p=self.top_p)
         caps = rollout_captions(ids, self.end_idx, cfg.pad_idx)  # [n, B, T]
         target = torch.as_tensor(batch_captions)[:, 1:].cpu().numpy()
         L = min(target.shape[1], caps.shape[-1] - 1)

@@ -2094,13 +2094,15 @@ struct capgen_engine {
   // cache.  Tokens are drawn to the end (<END> is not special, as in greedy); logp_out (nullable)
   // [R, max_length - 1]: each token's log-probability under the distribution it was drawn from.
   // The selection reads the f32 logits of either decode mode (sample_softmax, ops.hip); position t
-  // draws at site kSampleSite0 + t, above every dropout site (< 2048).
+  // draws at site kSampleSite0 + t, above every dropout site (< 2048).  top_p < 1 cuts each position's
+  // candidates to the nucleus (sample_nucleus, ops.hip); top_p == 1 launches sample_softmax as before.
   static constexpr uint32_t kSampleSite0 = 0x5A00;
   void sample(const void* feats, DType ft, const float* pos, int B, int N, int n, float temperature, int top_k,
-              uint64_t sd, int64_t* ids_out, float* logp_out, hipStream_t s) {
+              float top_p, uint64_t sd, int64_t* ids_out, float* logp_out, hipStream_t s) {
     require(n >= 1 && n <= 16, "sample: n_samples must be in [1, 16]");
     require(temperature > 0.f && temperature < INFINITY, "sample: temperature must be > 0 and finite");
     require(top_k >= 0 && top_k <= 16 && top_k <= L.V, "sample: top_k must be in [0, min(16, num_vocab)]");
+    require(top_p > 0.f && top_p <= 1.f, "sample: top_p must be in (0, 1]");
     require(B >= 1 && N >= 1 && N <= 64, "sample: need B >= 1 and N in [1, 64]");
     require((int64_t)n * B * L.V < ((int64_t)1 << 32), "sample: n_samples * B * num_vocab must be < 2^32");
     require(ids_out != nullptr, "sample: null ids_out");
@@ -2116,8 +2118,12 @@ struct capgen_engine {
     CAPGEN_HIP(hipGetLastError());
     for (int t = 0; t < L.maxlen - 1; ++t) {
       dec_step(R, B, N, t, g.cache, g.ids, false, s);
-      sample_softmax(g.logits, R, L.V, inv_tau, top_k, sd, kSampleSite0 + (uint32_t)t, ids_out, W, t + 1,
-                     g.ids + t + 1, Tc, logp_out, Tc - 1, t, s);
+      if (top_p == 1.f)
+        sample_softmax(g.logits, R, L.V, inv_tau, top_k, sd, kSampleSite0 + (uint32_t)t, ids_out, W, t + 1,
+                       g.ids + t + 1, Tc, logp_out, Tc - 1, t, s);
+      else
+        sample_nucleus(g.logits, R, L.V, inv_tau, top_k, top_p, sd, kSampleSite0 + (uint32_t)t, ids_out, W, t + 1,
+                       g.ids + t + 1, Tc, logp_out, Tc - 1, t, nullptr, s);
     }
   }
 
@@ -2543,7 +2549,19 @@ int capgen_sample(capgen_t* h, const void* feats, int ft, const float* pos, int 
     set_device(h);
     hipStream_t cs = (hipStream_t)stream;
     h->enter(cs);
-    h->sample(feats, dt(ft), pos, B, N, n_samples, temperature, top_k, sd, ids_out, logp_out, h->es);
+    h->sample(feats, dt(ft), pos, B, N, n_samples, temperature, top_k, 1.f, sd, ids_out, logp_out, h->es);
+    h->leave(cs);
+  });
+}
+
+int capgen_sample_nucleus(capgen_t* h, const void* feats, int ft, const float* pos, int B, int N, int n_samples,
+                          float temperature, int top_k, float top_p, uint64_t sd, int64_t* ids_out, float* logp_out,
+                          void* stream) {
+  return guarded([&] {
+    set_device(h);
+    hipStream_t cs = (hipStream_t)stream;
+    h->enter(cs);
+    h->sample(feats, dt(ft), pos, B, N, n_samples, temperature, top_k, top_p, sd, ids_out, logp_out, h->es);
     h->leave(cs);
   });
 }
@@ -2974,6 +2992,16 @@ int capgen_debug_sample_softmax(const float* logits, int R, int V, float inv_tau
   return guarded([&] {
     sample_softmax(logits, R, V, inv_tau, top_k, sd, site, ids_out, ids_ld, col, next_ids, next_ld, logp_out, logp_ld,
                    logp_col, (hipStream_t)stream);
+  });
+}
+
+int capgen_debug_sample_nucleus(const float* logits, int R, int V, float inv_tau, int top_k, float top_p, uint64_t sd,
+                                uint32_t site, int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids,
+                                int64_t next_ld, float* logp_out, int64_t logp_ld, int logp_col, int32_t* count_out,
+                                void* stream) {
+  return guarded([&] {
+    sample_nucleus(logits, R, V, inv_tau, top_k, top_p, sd, site, ids_out, ids_ld, col, next_ids, next_ld, logp_out,
+                   logp_ld, logp_col, count_out, (hipStream_t)stream);
   });
 }
 

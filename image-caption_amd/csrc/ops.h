@@ -126,6 +126,12 @@ void argmax_softmax(const float* logits, int B, int V, int64_t* ids_out, int64_t
 void sample_softmax(const float* logits, int R, int V, float inv_tau, int top_k, uint64_t seed, uint32_t site,
                     int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids, int64_t next_ld, float* logp_out,
                     int64_t logp_ld, int logp_col, hipStream_t s);
+// nucleus (top-p) sampling: sample_softmax with the candidate set cut to the columns v whose strictly
+// more likely columns hold less than top_p of the (top_k-renormalised) mass; top_p in (0, 1], 1 launches
+// sample_softmax's kernels.  count_out (optional): the size of each row's candidate set.  Definition: ops.hip.
+void sample_nucleus(const float* logits, int R, int V, float inv_tau, int top_k, float top_p, uint64_t seed,
+                    uint32_t site, int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids, int64_t next_ld,
+                    float* logp_out, int64_t logp_ld, int logp_col, int32_t* count_out, hipStream_t s);
 // one beam-search step (model.py:183-190): rows j*B + i (j < k_in) of logits [k_in*B][V]; the
 // k best (prev[j*B+i] + softmax or log-softmax (logsm) of row j*B+i at v) per image i ->
 // out_prob/src/tok[sel*B + i]; cand_v/cand_i: k_in*B*k scratch (each row's k finalists)

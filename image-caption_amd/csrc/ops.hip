@@ -1571,6 +1571,266 @@ void sample_softmax(const float* logits, int R, int V, float inv_tau, int top_k,
   CAPGEN_HIP(hipGetLastError());
 }
 
+// ---- nucleus (top-p) sampling: the selection above with the candidate set cut to a nucleus ----
+// One row of f32 logits [V], inv_tau, top_k, and top_p in (0, 1]:
+// - z_v = logits[v] * inv_tau, one f32 product, as sample_softmax.
+// - Base set C0: every v < V when top_k == 0.  Otherwise the top_k columns under (logit descending,
+//   v ascending), as sample_softmax.
+// - M = max over C0 of z_v, P = sum_{u in C0} exp(z_u - M), above(v) = sum_{u in C0, z_u > z_v}
+//   exp(z_u - M).  The inequality is strict.
+// - Candidate set: C = { v in C0 : above(v) < top_p * P }.  A word is kept exactly when the words
+//   strictly more likely than it do not already hold top_p of the mass.  C always holds the row's
+//   maximum and is nested in top_p.  Columns with bit-equal z are in or out together, so the set does
+//   not depend on column order (top_k may still cut a tie group by index, as sample_softmax).  With
+//   top_k > 0 the mass is the one renormalised over C0: top-k first, nucleus within it.
+// - top_p == 1 means C = C0 by definition, not by arithmetic: the launcher then launches
+//   sample_softmax_kernel itself, so tokens and log-probabilities are bit-identical to sample_softmax.
+// - Token: argmax over C of (z_v + g_v), first index on ties; g is exactly sample_softmax's noise
+//   (the same hash, counter r * V + v and site).  The draw is therefore coupled to the untruncated
+//   one: whenever the top_p = 1 winner lies in C, it is also the nucleus winner.
+// - Log-probability: logp = z_token - M_C - log sum_{v in C} exp(z_v - M_C), the log-probability
+//   under the distribution actually sampled (M_C = M, since C holds the maximum).  Exactly 0 when
+//   |C| = 1.
+// - Stores: as sample_softmax, and an optional count_out[r] = |C| (int32).  Nothing else is written.
+// top_k > 0: after sample_softmax_kernel's merge C0 sits one column per lane in wave 0; above(v) is
+// top_k lane broadcasts, summed in lane order.  top_k == 0: C is { v : key(z_v) >= k* } for the
+// order-preserving integer key of the f32 z (-0 counted as +0); k* is the smallest key with
+// mass_above(k*) < top_p * P, found by bisection of the 32-bit key range in exactly 32 steps, each one
+// fixed-order block sum (no atomics: one result per seed, bit for bit).  mass_above is a sum of
+// non-negative terms in a fixed order with some of them zeroed, so it is monotone in the key, and
+// mass_above(key(-inf)) is P bit for bit: a column whose exp underflows is never in C.  The register
+// form (NV = 40) keeps the row's keys and exponentials (80 VGPRs); the generic form recomputes them
+// from memory in every step.  Every trip count is a constant or V / 256.  A row of NaNs or infinities
+// leaves a NaN mass, every comparison false, and no winner: token 0, as sample_softmax.
+__device__ __forceinline__ uint32_t z_key(float z) {
+  const uint32_t b = (uint32_t)__float_as_int(z + 0.f);  // -0 -> +0
+  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float key_z(uint32_t k) {
+  return __int_as_float((int)(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)));
+}
+__device__ __forceinline__ int block_sum_int(int v, int* sh) {
+  v += __shfl_xor(v, 1, 64);
+  v += __shfl_xor(v, 2, 64);
+  v += __shfl_xor(v, 4, 64);
+  v += __shfl_xor(v, 8, 64);
+  v += __shfl_xor(v, 16, 64);
+  v += __shfl_xor(v, 32, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const int r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  __syncthreads();
+  return r;
+}
+
+template <int NV, int KM>
+__global__ void __launch_bounds__(256) sample_nucleus_kernel(const float* __restrict__ logits, int V, float inv_tau,
+                                                             int top_k, float top_p, uint64_t seed, uint32_t site,
+                                                             int64_t* ids_out, int64_t ids_ld, int col,
+                                                             int32_t* next_ids, int64_t next_ld, float* logp_out,
+                                                             int64_t logp_ld, int logp_col, int32_t* count_out) {
+  __shared__ float sh[4];
+  __shared__ float wv[4][16];
+  __shared__ int wi[4][16];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* x = logits + (int64_t)r * V;
+  const uint32_t key = drop_key(seed, site), base = (uint32_t)r * (uint32_t)V;
+  // the winner's (perturbed score, column, bits of its z); M, the exp-sum over C and |C|
+  float best = -INFINITY, mx = -INFINITY, se = 0.f;
+  int bidx = 0x7fffffff, bz = 0, cnt = 0;
+  bool writer = false;
+  if constexpr (KM == 0) {
+    uint32_t kr[NV > 0 ? NV : 1];  // key(z); 0 past the row's end
+    float er[NV > 0 ? NV : 1];     // exp(z - M); 0 past the row's end
+    if constexpr (NV > 0) {
+      float xr[NV];
+#pragma unroll
+      for (int u = 0; u < NV; ++u) {
+        const int c = tid + 256 * u;
+        xr[u] = c < V ? x[c] : -INFINITY;
+      }
+#pragma unroll
+      for (int u = 0; u < NV; ++u) {
+        const float z = __fmul_rn(xr[u], inv_tau);
+        if (tid + 256 * u < V) mx = fmaxf(mx, z);
+        kr[u] = tid + 256 * u < V ? z_key(z) : 0u;
+      }
+    } else {
+      for (int c = tid; c < V; c += 256) mx = fmaxf(mx, __fmul_rn(x[c], inv_tau));
+    }
+    mx = block_max(mx, sh);
+    float pe = 0.f;
+    if constexpr (NV > 0) {
+#pragma unroll
+      for (int u = 0; u < NV; ++u) {
+        er[u] = tid + 256 * u < V ? expf(key_z(kr[u]) - mx) : 0.f;
+        pe += er[u];
+      }
+    } else {
+      for (int c = tid; c < V; c += 256) pe += expf(__fmul_rn(x[c], inv_tau) - mx);
+    }
+    const float thr = __fmul_rn(top_p, block_sum(pe, sh));  // top_p * P
+    // the mass of the columns whose key is above k: the same per-thread order and block sum as P
+    auto mass_above = [&](uint32_t k) {
+      float a = 0.f;
+      if constexpr (NV > 0) {
+#pragma unroll
+        for (int u = 0; u < NV; ++u) a += kr[u] > k ? er[u] : 0.f;
+      } else {
+        for (int c = tid; c < V; c += 256) {
+          const float z = __fmul_rn(x[c], inv_tau);
+          a += z_key(z) > k ? expf(z - mx) : 0.f;
+        }
+      }
+      return block_sum(a, sh);
+    };
+    // k* = the smallest key k with mass_above(k) < top_p * P: [lo, hi] halves exactly 32 times
+    uint32_t lo = 0u, hi = 0xFFFFFFFFu;
+    for (int it = 0; it < 32; ++it) {
+      const uint32_t mid = lo + ((hi - lo) >> 1);
+      if (mass_above(mid) < thr) hi = mid;
+      else lo = mid + 1u;
+    }
+    auto visit = [&](uint32_t kz, float e, int c) {
+      if (kz < lo) return;
+      const float z = key_z(kz);
+      se += e;
+      ++cnt;
+      const float sc = z + gumbel_noise(key, base + (uint32_t)c);
+      if (sc > best) best = sc, bidx = c, bz = __float_as_int(z);
+    };
+    if constexpr (NV > 0) {
+#pragma unroll
+      for (int u = 0; u < NV; ++u)
+        if (tid + 256 * u < V) visit(kr[u], er[u], tid + 256 * u);
+    } else {
+      for (int c = tid; c < V; c += 256) {
+        const float z = __fmul_rn(x[c], inv_tau);
+        visit(z_key(z), expf(z - mx), c);
+      }
+    }
+    se = block_sum(se, sh);
+    cnt = block_sum_int(cnt, wi[0]);
+    wave_best(best, bidx, bz);
+    if (lane == 0) wv[wave][0] = best, wi[wave][0] = bidx, wi[wave][1] = bz;
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < 4; ++w)
+        if (wv[w][0] > best || (wv[w][0] == best && wi[w][0] < bidx)) best = wv[w][0], bidx = wi[w][0], bz = wi[w][1];
+      writer = true;
+    }
+  } else {
+    float tv[KM];
+    int ti[KM];
+#pragma unroll
+    for (int u = 0; u < KM; ++u) tv[u] = -INFINITY, ti[u] = 0x7fffffff;
+    if constexpr (NV > 0) {
+      float xr[NV];
+#pragma unroll
+      for (int u = 0; u < NV; ++u) {
+        const int c = tid + 256 * u;
+        xr[u] = c < V ? x[c] : -INFINITY;
+      }
+#pragma unroll
+      for (int u = 0; u < NV; ++u)
+        if (tid + 256 * u < V) topk_insert<KM>(tv, ti, xr[u], tid + 256 * u);
+    } else {
+      for (int c = tid; c < V; c += 256) topk_insert<KM>(tv, ti, x[c], c);
+    }
+    for (int sel = 0; sel < top_k; ++sel) {  // each wave's top_k best: the winner pops its list head
+      float hv = tv[0];
+      int hi = ti[0], hpos = lane;
+      wave_best(hv, hi, hpos);
+      if (lane == 0) wv[wave][sel] = hv, wi[wave][sel] = hi;
+      if (lane == hpos) {
+#pragma unroll
+        for (int u = 0; u + 1 < KM; ++u) tv[u] = tv[u + 1], ti[u] = ti[u + 1];
+        tv[KM - 1] = -INFINITY, ti[KM - 1] = 0x7fffffff;
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {  // the row's top_k of the waves' 4 top_k: lane sel keeps candidate sel
+      const bool on = lane < 4 * top_k;
+      float v = on ? wv[lane / top_k][lane % top_k] : -INFINITY;
+      int c = on ? wi[lane / top_k][lane % top_k] : 0x7fffffff;
+      float cx = -INFINITY;
+      int cc = 0x7fffffff;
+      for (int sel = 0; sel < top_k; ++sel) {
+        float hv = v;
+        int hi = c, hpos = lane;
+        wave_best(hv, hi, hpos);
+        if (lane == sel) cx = hv, cc = hi;
+        if (lane == hpos) v = -INFINITY, c = 0x7fffffff;
+      }
+      const bool in_c0 = lane < top_k;
+      const float z = in_c0 ? __fmul_rn(cx, inv_tau) : -INFINITY;
+      mx = wave_max(z);
+      const float e = in_c0 ? expf(z - mx) : 0.f;
+      // P and above(v) in one lane order, so that above(v) is P bit for bit under a column of no mass
+      float pe = 0.f, above = 0.f;
+#pragma unroll
+      for (int j = 0; j < KM; ++j) {  // lanes >= top_k hold z = -inf, e = 0
+        const float zj = __shfl(z, j, 64), ej = __shfl(e, j, 64);
+        pe += ej;
+        above += zj > z ? ej : 0.f;
+      }
+      const bool in_c = in_c0 && above < __fmul_rn(top_p, pe);
+      se = wave_sum(in_c ? e : 0.f);
+      cnt = __popcll(__ballot(in_c));
+      best = in_c ? z + gumbel_noise(key, base + (uint32_t)cc) : -INFINITY;
+      bidx = in_c ? cc : 0x7fffffff, bz = __float_as_int(z);
+      wave_best(best, bidx, bz);
+      writer = lane == 0;
+    }
+  }
+  if (writer) {
+    const int token = (unsigned)bidx < (unsigned)V ? bidx : 0;  // (a row of NaNs has no winner)
+    ids_out[(int64_t)r * ids_ld + col] = token;
+    if (next_ids) next_ids[(int64_t)r * next_ld] = token;
+    if (logp_out) logp_out[(int64_t)r * logp_ld + logp_col] = (__int_as_float(bz) - mx) - logf(se);
+    if (count_out) count_out[r] = cnt;
+  }
+}
+
+__global__ void fill_i32_kernel(int32_t* p, int n, int32_t v) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+using NucleusKernel = void (*)(const float*, int, float, int, float, uint64_t, uint32_t, int64_t*, int64_t, int,
+                               int32_t*, int64_t, float*, int64_t, int, int32_t*);
+template <int KM>
+static NucleusKernel sample_nucleus_form(int V) {
+  return V <= 256 * 40 ? sample_nucleus_kernel<40, KM> : sample_nucleus_kernel<0, KM>;
+}
+
+void sample_nucleus(const float* logits, int R, int V, float inv_tau, int top_k, float top_p, uint64_t seed,
+                    uint32_t site, int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids, int64_t next_ld,
+                    float* logp_out, int64_t logp_ld, int logp_col, int32_t* count_out, hipStream_t s) {
+  require(top_p > 0.f && top_p <= 1.f, "sample_nucleus: top_p must be in (0, 1]");  // (false for a NaN)
+  if (top_p == 1.f) {  // C = C0 by definition: sample_softmax's own kernels
+    sample_softmax(logits, R, V, inv_tau, top_k, seed, site, ids_out, ids_ld, col, next_ids, next_ld, logp_out, logp_ld,
+                   logp_col, s);
+    if (count_out) {
+      fill_i32_kernel<<<(R + 255) / 256, 256, 0, s>>>(count_out, R, top_k == 0 ? V : top_k);
+      CAPGEN_HIP(hipGetLastError());
+    }
+    return;
+  }
+  require(R >= 1 && V >= 1 && (int64_t)R * V < ((int64_t)1 << 32), "sample_nucleus: need R, V >= 1 and R * V < 2^32");
+  require(inv_tau > 0.f && inv_tau < INFINITY, "sample_nucleus: temperature must be > 0 and finite");
+  require(top_k >= 0 && top_k <= 16 && top_k <= V, "sample_nucleus: top_k must be in [0, min(16, num_vocab)]");
+  require(logits && ids_out && col >= 0 && logp_col >= 0, "sample_nucleus: null logits / ids_out or a negative column");
+  const NucleusKernel kern = top_k == 0   ? sample_nucleus_form<0>(V)
+                             : top_k <= 4 ? sample_nucleus_form<4>(V)
+                             : top_k == 5 ? sample_nucleus_form<5>(V)
+                             : top_k <= 8 ? sample_nucleus_form<8>(V)
+                                          : sample_nucleus_form<16>(V);
+  kern<<<R, 256, 0, s>>>(logits, V, inv_tau, top_k, top_p, seed, site, ids_out, ids_ld, col, next_ids, next_ld,
+                         logp_out, logp_ld, logp_col, count_out);
+  CAPGEN_HIP(hipGetLastError());
+}
+
 // ---- bf16 decode selection from slab stats (GemmArgs::dec_stats) ----------------------------
 // One wave per row, 4 rows per workgroup.  The row's ceil(V/16) slab stats (8 B each, 1/8 of the
 // f32 logits) sit NS per lane in registers: one pass gives the row max M and the exp-sum

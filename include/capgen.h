@@ -172,6 +172,17 @@ int capgen_beam(capgen_t* h, const void* feats, int feats_dtype, const float* po
  * [0, min(16, num_vocab)], N in [1, 64], n_samples * B * num_vocab < 2^32. */
 int capgen_sample(capgen_t* h, const void* feats, int feats_dtype, const float* pos, int B, int N, int n_samples,
                   float temperature, int top_k, uint64_t seed, int64_t* ids_out, float* logp_out, void* stream);
+/* capgen_sample with nucleus (top-p) truncation (Holtzman et al. 2020): position t draws from the
+ * candidates of capgen_sample (the top_k largest logits, or all) cut to the columns whose strictly more
+ * likely columns hold less than top_p of their softmax mass -- the smallest set of most likely words
+ * that reaches top_p, ties kept whole -- and renormalised; logp_out is the log-probability under that
+ * distribution (0 where one word is left).  Same noise, counters and sites as capgen_sample: a draw is
+ * the untruncated draw whenever that lies in the nucleus.  top_p in (0, 1]; top_p = 1 is capgen_sample,
+ * bit for bit (the same kernels).  Everything else as capgen_sample.  Definition: csrc/ops.hip.
+ * Added without a change of CAPGEN_ABI_VERSION: no existing entry changed (backward compatible). */
+int capgen_sample_nucleus(capgen_t* h, const void* feats, int feats_dtype, const float* pos, int B, int N,
+                          int n_samples, float temperature, int top_k, float top_p, uint64_t seed, int64_t* ids_out,
+                          float* logp_out, void* stream);
 
 /* Decode scoring of capgen_greedy / capgen_beam: 0 (default) = Transformer (argmax of Softmax,
  * beams accumulate probabilities, model.py:124-128,183); 1 = PolicyNetwork, the SCST model
@@ -415,6 +426,13 @@ int capgen_debug_argmax_softmax(const float* logits, int B, int V, int64_t* ids_
 int capgen_debug_sample_softmax(const float* logits, int R, int V, float inv_tau, int top_k, uint64_t seed,
                                 uint32_t site, int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids,
                                 int64_t next_ld, float* logp_out, int64_t logp_ld, int logp_col, void* stream);
+/* The selection of capgen_sample_nucleus: as capgen_debug_sample_softmax with the candidates cut to the
+ * nucleus of top_p in (0, 1] (1: the kernels of capgen_debug_sample_softmax); count_out (nullable):
+ * int32 [R], the size of each row's candidate set. */
+int capgen_debug_sample_nucleus(const float* logits, int R, int V, float inv_tau, int top_k, float top_p,
+                                uint64_t seed, uint32_t site, int64_t* ids_out, int64_t ids_ld, int col,
+                                int32_t* next_ids, int64_t next_ld, float* logp_out, int64_t logp_ld, int logp_col,
+                                int32_t* count_out, void* stream);
 int capgen_debug_slab_argmax(const float* logits, const void* stats, int B, int V, int64_t* ids_out, int64_t ids_ld,
                              int col, int32_t* next_ids, int64_t next_ld, void* stream);
 int capgen_debug_beam_step_topk(const float* logits, const void* stats, const float* prev, int k_in, int B, int V,
