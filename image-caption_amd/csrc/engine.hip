@@ -30,6 +30,7 @@
 #include "layout.h"
 #include "ops.h"
 #include "qkv_attn.h"
+#include "select.h"
 #include "variants.h"
 #include "rl.h"
 
@@ -175,36 +176,6 @@ struct GenWS {
   float *bprob, *bprob2;
   int32_t *bsrc, *btok;
 };
-
-__global__ void init_gen_ids_kernel(int64_t* out, int rows, int width, int32_t* ids, int tcap) {
-  int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < rows * width) out[c] = (c % width) == 0 ? 1 : 0;
-  if (c < rows * tcap) ids[c] = (c % tcap) == 0 ? 1 : 0;
-}
-
-// dst row r = (j, i) <- src row (src[j][i], i); then optionally set column `col` to tok
-template <typename E>
-__global__ void beam_gather_kernel(const E* __restrict__ src, E* __restrict__ dst, int64_t row_elems,
-                                   int64_t copy_elems, const int32_t* __restrict__ bsrc, int B, int R,
-                                   const int32_t* __restrict__ tok, int col) {
-  const int r = blockIdx.y;
-  const int srow = bsrc[r] * B + (r % B);
-  const E* s = src + (int64_t)srow * row_elems;
-  E* d = dst + (int64_t)r * row_elems;
-  for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < copy_elems; c += (int64_t)gridDim.x * blockDim.x)
-    d[c] = (tok && c == col) ? (E)tok[r] : s[c];
-}
-
-// beam reorder of the K/V row table (attention kv_row): row r's positions 0..t come from its
-// source beam's row, position t + 1 (written by row r's own next decoder step) is row r
-__global__ void beam_kvrow_kernel(const int32_t* __restrict__ src, int32_t* __restrict__ dst, int Tc, int t,
-                                  const int32_t* __restrict__ bsrc, int B, int R) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= R * Tc) return;
-  const int r = e / Tc, c = e % Tc;
-  const int srow = bsrc[r] * B + (r % B);
-  dst[e] = c <= t ? src[(int64_t)srow * Tc + c] : (c == t + 1 ? r : 0);
-}
 
 }  // namespace
 
@@ -2010,8 +1981,7 @@ struct capgen_engine {
     encode_only(feats, ft, pos, B, N, s);
     build_dtiles(s);
     const int Tc = L.maxlen, W = L.maxlen + 1;
-    init_gen_ids_kernel<<<(B * std::max(W, Tc) + 255) / 256, 256, 0, s>>>(ids_out, B, W, g.ids, Tc);
-    CAPGEN_HIP(hipGetLastError());
+    init_gen_ids(ids_out, B, W, g.ids, Tc, s);
     for (int t = 0; t < L.maxlen - 1; ++t) {
       dec_step(B, B, N, t, g.cache, g.ids, attn_out != nullptr, s);
       if (attn_out) attention_head_mean(g.Pc, B, L.Hd, 1, N, 0, attn_out + (int64_t)t * B * N, s);
@@ -2032,10 +2002,9 @@ struct capgen_engine {
     const int R = k * B, Tc = L.maxlen, Tw = L.maxlen;
     encode_only(feats, ft, pos, B, N, s);
     build_dtiles(s);
-    init_gen_ids_kernel<<<(R * Tc + 255) / 256, 256, 0, s>>>(g.seq, R, Tw, g.ids, Tc);
-    CAPGEN_HIP(hipGetLastError());
+    init_gen_ids(g.seq, R, Tw, g.ids, Tc, s);  // (Tw == Tc)
     // position 0: every beam holds <START>; top-k of beam 0's distribution (model.py:148-166)
-    beam_kvrow_kernel<<<(R * Tc + 255) / 256, 256, 0, s>>>(g.kvrow2, g.kvrow, Tc, -1, g.ids, B, R);  // [r][0] = r
+    beam_kvrow(g.kvrow2, g.kvrow, Tc, -1, g.ids, B, R, s);  // [r][0] = r
     dec_step(R, B, N, 0, g.cache, g.ids, false, s);
     // bf16: the selection and the reorder of a step as one launch per image (beam_slab_step:
     // CAPGEN_FUSED_BEAM_STEP=0 restores the top-k, merge and three reorder launches)
@@ -2060,11 +2029,9 @@ struct capgen_engine {
     // reorder moves only the ids / sequences and this [R][Tc] table
     auto reorder = [&](int t) {
       // seq/ids rows follow their source beam, then column t+1 = chosen token
-      dim3 gs(1, R);
-      beam_gather_kernel<int64_t><<<gs, 64, 0, s>>>(g.seq, g.seq2, Tw, Tw, g.bsrc, B, R, g.btok, t + 1);
-      beam_gather_kernel<int32_t><<<gs, 64, 0, s>>>(g.ids, g.ids2, Tc, Tc, g.bsrc, B, R, g.btok, t + 1);
-      beam_kvrow_kernel<<<(R * Tc + 255) / 256, 256, 0, s>>>(g.kvrow, g.kvrow2, Tc, t, g.bsrc, B, R);
-      CAPGEN_HIP(hipGetLastError());
+      beam_gather(g.seq, g.seq2, Tw, g.bsrc, B, R, g.btok, t + 1, s);
+      beam_gather(g.ids, g.ids2, Tc, g.bsrc, B, R, g.btok, t + 1, s);
+      beam_kvrow(g.kvrow, g.kvrow2, Tc, t, g.bsrc, B, R, s);
       std::swap(g.seq, g.seq2);
       std::swap(g.ids, g.ids2);
       std::swap(g.kvrow, g.kvrow2);
@@ -2093,9 +2060,9 @@ struct capgen_engine {
   // (0: the whole vocabulary), rows j * B + b as beam's, one encoder pass, every row its own K/V
   // cache.  Tokens are drawn to the end (<END> is not special, as in greedy); logp_out (nullable)
   // [R, max_length - 1]: each token's log-probability under the distribution it was drawn from.
-  // The selection reads the f32 logits of either decode mode (sample_softmax, ops.hip); position t
+  // The selection reads the f32 logits of either decode mode (sample_softmax, select.hip); position t
   // draws at site kSampleSite0 + t, above every dropout site (< 2048).  top_p < 1 cuts each position's
-  // candidates to the nucleus (sample_nucleus, ops.hip); top_p == 1 launches sample_softmax as before.
+  // candidates to the nucleus (sample_nucleus, select.hip); top_p == 1 launches sample_softmax as before.
   static constexpr uint32_t kSampleSite0 = 0x5A00;
   void sample(const void* feats, DType ft, const float* pos, int B, int N, int n, float temperature, int top_k,
               float top_p, uint64_t sd, int64_t* ids_out, float* logp_out, hipStream_t s) {
@@ -2114,8 +2081,7 @@ struct capgen_engine {
     ensure_dtiles();
     encode_only(feats, ft, pos, B, N, s);
     build_dtiles(s);
-    init_gen_ids_kernel<<<(R * std::max(W, Tc) + 255) / 256, 256, 0, s>>>(ids_out, R, W, g.ids, Tc);
-    CAPGEN_HIP(hipGetLastError());
+    init_gen_ids(ids_out, R, W, g.ids, Tc, s);
     for (int t = 0; t < L.maxlen - 1; ++t) {
       dec_step(R, B, N, t, g.cache, g.ids, false, s);
       if (top_p == 1.f)

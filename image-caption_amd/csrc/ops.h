@@ -117,44 +117,6 @@ void grad_norm_finish(const double* partials, int n_slots, double* sum, const fl
 void to_bf16(const float* src, bf16* dst, size_t n, hipStream_t s);
 // exact, order-independent checksum of an f32 arena (sum of bit patterns x (2 i + 1) mod 2^64); synchronous
 uint64_t arena_checksum(const float* p, size_t n, hipStream_t s);
-// greedy: out token = argmax(softmax(logits[b])) (first index on ties)   (model.py:126-128)
-void argmax_softmax(const float* logits, int B, int V, int64_t* ids_out, int64_t ids_ld, int col,
-                    int32_t* next_ids, int64_t next_ld, hipStream_t s, int logsm = 0);
-// sampled decoding: token of row r ~ softmax(logits[r] * inv_tau) restricted to the row's top_k logits
-// (top_k = 0: every column), drawn by Gumbel-max from the counter hash of (seed, site, r * V + v);
-// logp_out (optional): its log-probability under that distribution.  Definition: ops.hip.
-void sample_softmax(const float* logits, int R, int V, float inv_tau, int top_k, uint64_t seed, uint32_t site,
-                    int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids, int64_t next_ld, float* logp_out,
-                    int64_t logp_ld, int logp_col, hipStream_t s);
-// nucleus (top-p) sampling: sample_softmax with the candidate set cut to the columns v whose strictly
-// more likely columns hold less than top_p of the (top_k-renormalised) mass; top_p in (0, 1], 1 launches
-// sample_softmax's kernels.  count_out (optional): the size of each row's candidate set.  Definition: ops.hip.
-void sample_nucleus(const float* logits, int R, int V, float inv_tau, int top_k, float top_p, uint64_t seed,
-                    uint32_t site, int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids, int64_t next_ld,
-                    float* logp_out, int64_t logp_ld, int logp_col, int32_t* count_out, hipStream_t s);
-// one beam-search step (model.py:183-190): rows j*B + i (j < k_in) of logits [k_in*B][V]; the
-// k best (prev[j*B+i] + softmax or log-softmax (logsm) of row j*B+i at v) per image i ->
-// out_prob/src/tok[sel*B + i]; cand_v/cand_i: k_in*B*k scratch (each row's k finalists)
-void beam_step_topk(const float* logits, const float* prev, int k_in, int B, int V, int k, int logsm, float* cand_v,
-                    int32_t* cand_i, float* out_prob, int32_t* out_src, int32_t* out_tok, hipStream_t s);
-// bf16 decode selection from the classifier epilogue's slab stats (GemmArgs::dec_stats: {max,
-// sum exp(v - max)} per row and 16-column slab, stats row stride S = ceil(V / 16)):
-// greedy -- argmax of the logits (first index on ties), read from the best slab only;
-// beam -- each row's k best scores from its k best slabs (every top-k element lies in the k
-// slabs with the largest maxima under (max desc, slab asc)), then the per-image merge.
-// V <= 16384 (S <= 1024 slabs, 16 per lane in registers).
-bool slab_select_ok(int V);
-void slab_argmax(const float* logits, const float2* stats, int B, int V, int64_t* ids_out, int64_t ids_ld, int col,
-                 int32_t* next_ids, int64_t next_ld, hipStream_t s);
-// the bf16 beam step of every image in one launch (slab selection + merge + the reorder of the sequences,
-// ids and K/V row table into the *_dst buffers, chosen token at column t + 1; ops.hip)
-void beam_slab_step(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
-                    int logsm, float* out_prob, int32_t* out_src, int32_t* out_tok, const int64_t* seq_src,
-                    int64_t* seq_dst, int Tw, const int32_t* ids_src, int32_t* ids_dst, const int32_t* kv_src,
-                    int32_t* kv_dst, int Tc, int t, hipStream_t s);
-void beam_step_topk_slab(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
-                         int logsm, float* cand_v, int32_t* cand_i, float* out_prob, int32_t* out_src,
-                         int32_t* out_tok, hipStream_t s);
 void bump_seed(uint64_t* seed, hipStream_t s);
 
 }  // namespace capgen

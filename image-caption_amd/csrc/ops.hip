@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "ops.h"
+#include "select_dev.h"  // block reductions
 #include "hazard.h"
 
 namespace capgen {
@@ -524,24 +525,6 @@ void stripe_reduce(float* S, int stripes, int64_t stride, int64_t n, float* dst,
   CAPGEN_HIP(hipGetLastError());
 }
 
-// ---- block reductions (256 threads = 4 waves) ----
-__device__ __forceinline__ float block_max(float v, float* sh) {
-  v = wave_max(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return r;
-}
-
 // WT (all three CE kernels): the row's loss and gradient are scaled by the per-caption weight
 // row_w[m / rows_per_w] (capgen_train_step_weighted); WT = false is the unweighted code, row_w unread.
 template <typename T, bool WT>
@@ -565,7 +548,7 @@ __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logit
   mx = block_max(mx, sh);
   float se = 0.f;
   for (int c = threadIdx.x; c < V; c += 256) se += expf(x[c] - mx);
-  se = block_sum(se, sh);
+  se = block_sum_pairwise(se, sh);
   const float inv = 1.f / se;
   for (int c = threadIdx.x; c < V; c += 256) {
     float p = expf(x[c] - mx) * inv;
@@ -613,7 +596,7 @@ __global__ void __launch_bounds__(256) ce_reg_kernel(const float* __restrict__ l
     v[u].x = expf(v[u].x - mx), v[u].y = expf(v[u].y - mx), v[u].z = expf(v[u].z - mx), v[u].w = expf(v[u].w - mx);
     se += (v[u].x + v[u].y) + (v[u].z + v[u].w);
   }
-  se = block_sum(se, sh);
+  se = block_sum_pairwise(se, sh);
   const float inv = 1.f / se;
 #pragma unroll
   for (int u = 0; u < NV4; ++u) {
@@ -718,7 +701,7 @@ __global__ void __launch_bounds__(256) ce_finish_kernel(const float2* __restrict
   float se = 0.f;
 #pragma unroll
   for (int u = 0; u < SPT; ++u) se += st[u].y == 0.f ? 0.f : st[u].y * expf(st[u].x - mx);
-  se = block_sum(se, sh);
+  se = block_sum_pairwise(se, sh);
   const float lse = mx + logf(se);
 #pragma unroll
   for (int u = 0; u < SPT; ++u) {
@@ -786,7 +769,7 @@ __global__ void loss_finalize_kernel(const float* __restrict__ loss_row, int M, 
   float acc = 0.f;
   if (!ce_in)
     for (int c = threadIdx.x; c < M; c += 256) acc += loss_row[c];
-  acc = block_sum(acc, sh);
+  acc = block_sum_pairwise(acc, sh);
   if (threadIdx.x == 0) {
     const float n = *count;
     const float ce = ce_in ? *ce_in : acc / n;
@@ -1101,986 +1084,6 @@ void to_bf16(const float* src, bf16* dst, size_t n, hipStream_t s) {
   }
   int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
   to_bf16_kernel<<<grid, 256, 0, s>>>(src, dst, n);
-  CAPGEN_HIP(hipGetLastError());
-}
-
-// ---- greedy / beam helpers ---------------------------------------------------------
-// logsm = 0: argmax of Softmax (Transformer, model.py:124-128); 1: of LogSoftmax
-// (PolicyNetwork, model_RL.py:72,126-127) -- the same token except where the rounding of the
-// two scores makes different near-ties
-// NV > 0: the row (V <= 256 NV) is read once into registers, every load up front (one memory
-// round trip instead of three dependent passes); the same per-thread order as the NV = 0 loops
-template <int NV>
-__global__ void __launch_bounds__(256) argmax_softmax_kernel(const float* __restrict__ logits, int V,
-                                                             int64_t* ids_out, int64_t ids_ld, int col,
-                                                             int32_t* next_ids, int64_t next_ld, int logsm) {
-  __shared__ float sh[4];
-  __shared__ float bv[4];
-  __shared__ int bi[4];
-  const int b = blockIdx.x;
-  const float* x = logits + (int64_t)b * V;
-  float xr[NV > 0 ? NV : 1];
-  float mx = -INFINITY;
-  if constexpr (NV > 0) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int c = threadIdx.x + 256 * u;
-      xr[u] = c < V ? x[c] : -INFINITY;
-      mx = fmaxf(mx, xr[u]);
-    }
-  } else {
-    for (int c = threadIdx.x; c < V; c += 256) mx = fmaxf(mx, x[c]);
-  }
-  mx = block_max(mx, sh);
-  float se = 0.f;
-  if constexpr (NV > 0) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u)
-      if (threadIdx.x + 256 * u < V) se += expf(xr[u] - mx);
-  } else {
-    for (int c = threadIdx.x; c < V; c += 256) se += expf(x[c] - mx);
-  }
-  se = block_sum(se, sh);
-  // argmax over the softmax probabilities, first index on ties (torch.argmax)
-  float best = -INFINITY;
-  int bidx = 0x7fffffff;
-  const float lse = logf(se);
-  if constexpr (NV > 0) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int c = threadIdx.x + 256 * u;
-      if (c < V) {
-        const float p = logsm ? (xr[u] - mx) - lse : expf(xr[u] - mx) / se;
-        if (p > best) {
-          best = p;
-          bidx = c;
-        }
-      }
-    }
-  } else {
-    for (int c = threadIdx.x; c < V; c += 256) {
-      const float p = logsm ? (x[c] - mx) - lse : expf(x[c] - mx) / se;
-      if (p > best) {
-        best = p;
-        bidx = c;
-      }
-    }
-  }
-  auto merge = [&](float ov, int oi) {
-    if (ov > best || (ov == best && oi < bidx)) {
-      best = ov;
-      bidx = oi;
-    }
-  };
-  merge(lane_xchg<32>(best), lane_xchg<32>(bidx));
-  merge(lane_xchg<16>(best), lane_xchg<16>(bidx));
-  merge(lane_xchg<8>(best), lane_xchg<8>(bidx));
-  merge(lane_xchg<4>(best), lane_xchg<4>(bidx));
-  merge(lane_xchg<2>(best), lane_xchg<2>(bidx));
-  merge(lane_xchg<1>(best), lane_xchg<1>(bidx));
-  if ((threadIdx.x & 63) == 0) {
-    bv[threadIdx.x >> 6] = best;
-    bi[threadIdx.x >> 6] = bidx;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    best = bv[0];
-    bidx = bi[0];
-    for (int w = 1; w < 4; ++w)
-      if (bv[w] > best || (bv[w] == best && bi[w] < bidx)) {
-        best = bv[w];
-        bidx = bi[w];
-      }
-    ids_out[(int64_t)b * ids_ld + col] = bidx;
-    if (next_ids) next_ids[(int64_t)b * next_ld] = bidx;
-  }
-}
-void argmax_softmax(const float* logits, int B, int V, int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids,
-                    int64_t next_ld, hipStream_t s, int logsm) {
-  if (V <= 256 * 40) argmax_softmax_kernel<40><<<B, 256, 0, s>>>(logits, V, ids_out, ids_ld, col, next_ids, next_ld, logsm);
-  else argmax_softmax_kernel<0><<<B, 256, 0, s>>>(logits, V, ids_out, ids_ld, col, next_ids, next_ld, logsm);
-  CAPGEN_HIP(hipGetLastError());
-}
-
-// ---- beam search step (model.py:183-190; PolicyNetwork model_RL.py:182-190 with logsm) ----
-// Candidate (j, v) of image i scores prev[j][i] + p[j*B+i][v] (p: Softmax, or LogSoftmax with
-// logsm); the k best under (score desc, flat index j*V + v asc) -- a strict total order, so the
-// selection equals a full sort's first k.  Part 1, one workgroup per decoder row r = j*B + i:
-// the row's softmax exactly as a separate softmax pass would compute it (same strided
-// per-thread order and block reductions: the scores are bit-identical), the row held in
-// registers (NV values per thread; NV = 0 re-reads it from memory), each thread's sorted
-// top-KM, and the row's top k.  Part 2, one wave per image: top k of its k_in rows' k
-// finalists each -- every image-level winner is in its row's top k.  Neither the [R, V]
-// probabilities nor a [B, k*V] scan exist: one read of the logits per step.
-
-// sorted (desc) register top-KM insert of candidate (x, c)
-template <int KM>
-__device__ __forceinline__ void topk_insert(float (&tv)[KM], int (&ti)[KM], float x, int c) {
-  if (!(x > tv[KM - 1] || (x == tv[KM - 1] && c < ti[KM - 1]))) return;
-  float cv = x;
-  int ci = c;
-#pragma unroll
-  for (int u = 0; u < KM; ++u) {  // unrolled: no dynamic register indexing
-    const bool better = cv > tv[u] || (cv == tv[u] && ci < ti[u]);
-    const float ov = tv[u];
-    const int oi = ti[u];
-    tv[u] = better ? cv : ov;
-    ti[u] = better ? ci : oi;
-    cv = better ? ov : cv;
-    ci = better ? oi : ci;
-  }
-}
-
-// (value, index) winner of a wave: value desc, index asc; pos rides along
-template <int O>
-__device__ __forceinline__ void best_step(float& best, int& bidx, int& bpos) {
-  const float ov = lane_xchg<O>(best);
-  const int oi = lane_xchg<O>(bidx);
-  const int op = lane_xchg<O>(bpos);
-  if (ov > best || (ov == best && oi < bidx)) best = ov, bidx = oi, bpos = op;
-}
-__device__ __forceinline__ void wave_best(float& best, int& bidx, int& bpos) {
-  best_step<32>(best, bidx, bpos);
-  best_step<16>(best, bidx, bpos);
-  best_step<8>(best, bidx, bpos);
-  best_step<4>(best, bidx, bpos);
-  best_step<2>(best, bidx, bpos);
-  best_step<1>(best, bidx, bpos);
-}
-
-template <int W>
-__device__ __forceinline__ float blk_max(float v, float* sh) {
-  v = wave_max(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = sh[0];
-#pragma unroll
-  for (int w = 1; w < W; ++w) r = fmaxf(r, sh[w]);
-  __syncthreads();
-  return r;
-}
-template <int W>
-__device__ __forceinline__ float blk_sum(float v, float* sh) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = 0.f;
-#pragma unroll
-  for (int w = 0; w < W; ++w) r += sh[w];
-  __syncthreads();
-  return r;
-}
-
-// NT threads per row (W = NT / 64 waves), NV values per thread in registers (V <= NT * NV)
-template <int KM, int NV, int NT = 256>
-__global__ void __launch_bounds__(NT) beam_row_topk_kernel(const float* __restrict__ logits,
-                                                            const float* __restrict__ prev, int B, int V, int k,
-                                                            int logsm, float* __restrict__ cand_v,
-                                                            int* __restrict__ cand_i) {
-  constexpr int W = NT / 64;
-  __shared__ float sh[W];
-  __shared__ float wv[W][16];
-  __shared__ int wi[W][16];
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = r / B;
-  const float* x = logits + (int64_t)r * V;
-  float xr[NV > 0 ? NV : 1];
-  float mx = -INFINITY;
-  if constexpr (NV > 0) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int c = tid + NT * u;
-      xr[u] = c < V ? x[c] : -INFINITY;
-      mx = fmaxf(mx, xr[u]);
-    }
-  } else {
-    for (int c = tid; c < V; c += NT) mx = fmaxf(mx, x[c]);
-  }
-  mx = blk_max<W>(mx, sh);
-  float se = 0.f;
-  if constexpr (NV > 0) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u)
-      if (tid + NT * u < V) {
-        const float e = expf(xr[u] - mx);
-        se += e;
-        if (!logsm) xr[u] = e;  // Softmax scores need only exp(x - max)
-      }
-  } else {
-    for (int c = tid; c < V; c += NT) se += expf(x[c] - mx);
-  }
-  se = blk_sum<W>(se, sh);
-  const float lse = logf(se), add = prev ? prev[r] : 0.f;
-  float tv[KM];
-  int ti[KM];
-#pragma unroll
-  for (int u = 0; u < KM; ++u) tv[u] = -INFINITY, ti[u] = 0x7fffffff;
-  if constexpr (NV > 0) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int c = tid + NT * u;
-      if (c < V) topk_insert<KM>(tv, ti, (logsm ? (xr[u] - mx) - lse : xr[u] / se) + add, j * V + c);
-    }
-  } else {
-    for (int c = tid; c < V; c += NT)
-      topk_insert<KM>(tv, ti, (logsm ? (x[c] - mx) - lse : expf(x[c] - mx) / se) + add, j * V + c);
-  }
-  // the row's k best: k rounds of a wave argmax over the lanes' list heads (the winner pops its
-  // head) give each wave's k best; wave 0 then selects the row's k from the 4 k of them
-  for (int sel = 0; sel < k; ++sel) {
-    float best = tv[0];
-    int bidx = ti[0], bpos = lane;
-    wave_best(best, bidx, bpos);
-    if (lane == 0) wv[wave][sel] = best, wi[wave][sel] = bidx;
-    if (lane == bpos) {
-#pragma unroll
-      for (int u = 0; u + 1 < KM; ++u) tv[u] = tv[u + 1], ti[u] = ti[u + 1];
-      tv[KM - 1] = -INFINITY, ti[KM - 1] = 0x7fffffff;
-    }
-  }
-  __syncthreads();
-  if (wave == 0) {
-    const bool on = lane < W * k;
-    float v = on ? wv[lane / k][lane % k] : -INFINITY;
-    int c = on ? wi[lane / k][lane % k] : 0x7fffffff;
-    for (int sel = 0; sel < k; ++sel) {
-      float best = v;
-      int bidx = c, bpos = lane;
-      wave_best(best, bidx, bpos);
-      if (lane == 0) cand_v[(int64_t)r * k + sel] = best, cand_i[(int64_t)r * k + sel] = bidx;
-      if (lane == bpos) v = -INFINITY, c = 0x7fffffff;
-    }
-  }
-}
-
-// one wave per image: the k best of its k_in * k row finalists (k_in * k <= 256)
-__global__ void __launch_bounds__(64) beam_merge_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
-                                                        int k_in, int B, int V, int k, float* __restrict__ out_prob,
-                                                        int32_t* __restrict__ out_src, int32_t* __restrict__ out_tok) {
-  const int i = blockIdx.x, lane = threadIdx.x, n = k_in * k;
-  float v[4];
-  int c[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int e = lane + 64 * u;  // entry e = (row j = e / k, rank e % k)
-    const bool on = e < n;
-    const int64_t src = ((int64_t)(e / k) * B + i) * k + e % k;
-    v[u] = on ? cand_v[src] : -INFINITY;
-    c[u] = on ? cand_i[src] : 0x7fffffff;
-  }
-  for (int sel = 0; sel < k; ++sel) {
-    float best = -INFINITY;
-    int bidx = 0x7fffffff, bpos = -1;
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (v[u] > best || (v[u] == best && c[u] < bidx)) best = v[u], bidx = c[u], bpos = lane + 64 * u;
-    wave_best(best, bidx, bpos);
-    if (lane == 0) {
-      out_prob[sel * B + i] = best;
-      out_src[sel * B + i] = bidx / V;
-      out_tok[sel * B + i] = bidx % V;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (bpos == lane + 64 * u) v[u] = -INFINITY, c[u] = 0x7fffffff;
-  }
-}
-
-template <int KM>
-static void beam_row_topk(const float* logits, const float* prev, int rows, int B, int V, int k, int logsm,
-                          float* cand_v, int32_t* cand_i, hipStream_t s) {
-  // 512 threads per row where the row fits 20 values per thread (42 vs 50 us per token at B = 1280
-  // with 256 threads, round 2)
-  if (V <= 512 * 20 && KM * 8 <= 64)
-    beam_row_topk_kernel<KM, 20, 512><<<rows, 512, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i);
-  else if (V <= 256 * 40) beam_row_topk_kernel<KM, 40><<<rows, 256, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i);
-  else beam_row_topk_kernel<KM, 0><<<rows, 256, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i);
-}
-
-void beam_step_topk(const float* logits, const float* prev, int k_in, int B, int V, int k, int logsm, float* cand_v,
-                    int32_t* cand_i, float* out_prob, int32_t* out_src, int32_t* out_tok, hipStream_t s) {
-  require(k >= 1 && k <= 16 && k_in >= 1 && k_in * k <= 256, "beam_step_topk: k in [1, 16]");
-  const int rows = k_in * B;
-  if (k <= 4) beam_row_topk<4>(logits, prev, rows, B, V, k, logsm, cand_v, cand_i, s);
-  else if (k == 5) beam_row_topk<5>(logits, prev, rows, B, V, k, logsm, cand_v, cand_i, s);
-  else if (k <= 8) beam_row_topk<8>(logits, prev, rows, B, V, k, logsm, cand_v, cand_i, s);
-  else beam_row_topk<16>(logits, prev, rows, B, V, k, logsm, cand_v, cand_i, s);
-  beam_merge_kernel<<<B, 64, 0, s>>>(cand_v, cand_i, k_in, B, V, k, out_prob, out_src, out_tok);
-  CAPGEN_HIP(hipGetLastError());
-}
-
-// ---- sampled decoding: temperature / top-k sampling by Gumbel-max, with the log-probability ----
-// One launch per decode position, one 256-thread workgroup per row r of logits [R][V] (f32):
-// - Scaled logits.  z_v = logits[r][v] * inv_tau (f32), with inv_tau = 1 / temperature.
-// - Candidate set C.  Every v < V when top_k == 0.  Otherwise the top_k columns of the row under
-//   (logit descending, v ascending), with 1 <= top_k <= min(16, V).
-// - Noise.  h = mix32(seed, site, (uint32_t)(r * V + v)), then u = ((h >> 9) + 0.5f) * 2^-23, then
-//   g = -logf(-logf(u)).  u is exact in f32 and lies strictly inside (0, 1).  logf, not the __logf
-//   intrinsic: the winning column usually has u close to 1, where -log u is 1e-4 ... 6e-8, and the
-//   intrinsic's absolute error is of that size.  r is the row index within the launch; the launcher
-//   requires R * V < 2^32.
-// - Token.  token = argmax over v in C of (z_v + g_v), first index on ties.  With top_k == 1 this is
-//   the argmax of the logits, first index on ties.
-// - Log-probability.  logp = z_token - M - log sum_{v in C} exp(z_v - M), with M = max over C of z_v:
-//   the log-probability under the distribution actually sampled.  Exactly 0 for top_k == 1.
-// - Stores.  ids_out[r * ids_ld + col] = token (int64); next_ids[r * next_ld] = token (int32,
-//   optional); logp_out[r * logp_ld + logp_col] = logp (optional).  Nothing else is written.
-// Gumbel-max rather than an inverse-CDF scan: one pass, a result that does not depend on the
-// summation order, and an index a float64 restatement predicts exactly wherever the two best
-// perturbed scores are not within rounding of each other.  The slab statistics of the bf16 greedy /
-// beam selection are not used: their per-slab exp-sums hold at temperature 1 only.
-// NV > 0: the row (V <= 256 NV) is read once into registers, every load up front (as
-// argmax_softmax_kernel); KM > 0: the candidate set is the row's top_k <= KM, found as
-// beam_row_topk_kernel finds a row's k best (per-thread sorted lists, k wave rounds, wave 0 merges).
-__device__ __forceinline__ float gumbel_noise(uint32_t key, uint32_t idx) {
-  const uint32_t h = lowbias32(idx ^ key);  // mix32(seed, site, idx), the key hoisted
-  const float u = ((float)(h >> 9) + 0.5f) * 0x1p-23f;
-  return -logf(-logf(u));
-}
-
-template <int NV, int KM>
-__global__ void __launch_bounds__(256) sample_softmax_kernel(const float* __restrict__ logits, int V, float inv_tau,
-                                                             int top_k, uint64_t seed, uint32_t site,
-                                                             int64_t* ids_out, int64_t ids_ld, int col,
-                                                             int32_t* next_ids, int64_t next_ld, float* logp_out,
-                                                             int64_t logp_ld, int logp_col) {
-  __shared__ float sh[4];
-  __shared__ float wv[4][16];
-  __shared__ int wi[4][16];
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* x = logits + (int64_t)r * V;
-  const uint32_t key = drop_key(seed, site), base = (uint32_t)r * (uint32_t)V;
-  float xr[NV > 0 ? NV : 1];
-  if constexpr (NV > 0) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int c = tid + 256 * u;
-      xr[u] = c < V ? x[c] : -INFINITY;
-    }
-  }
-  // the winner's (perturbed score, column, bits of its z); M and the exp-sum over C
-  float best = -INFINITY, mx = -INFINITY, se = 0.f;
-  int bidx = 0x7fffffff, bz = 0;
-  bool writer = false;
-  if constexpr (KM == 0) {
-    auto visit = [&](float xv, int c) {
-      const float z = __fmul_rn(xv, inv_tau);  // (not contracted into the add: z is an f32)
-      mx = fmaxf(mx, z);
-      const float sc = z + gumbel_noise(key, base + (uint32_t)c);
-      if (sc > best) best = sc, bidx = c, bz = __float_as_int(z);
-    };
-    if constexpr (NV > 0) {
-#pragma unroll
-      for (int u = 0; u < NV; ++u)
-        if (tid + 256 * u < V) visit(xr[u], tid + 256 * u);
-    } else {
-      for (int c = tid; c < V; c += 256) visit(x[c], c);
-    }
-    mx = block_max(mx, sh);
-    if constexpr (NV > 0) {
-#pragma unroll
-      for (int u = 0; u < NV; ++u)
-        if (tid + 256 * u < V) se += expf(__fmul_rn(xr[u], inv_tau) - mx);
-    } else {
-      for (int c = tid; c < V; c += 256) se += expf(__fmul_rn(x[c], inv_tau) - mx);
-    }
-    se = block_sum(se, sh);
-    wave_best(best, bidx, bz);
-    if (lane == 0) wv[wave][0] = best, wi[wave][0] = bidx, wi[wave][1] = bz;
-    __syncthreads();
-    if (tid == 0) {
-      for (int w = 1; w < 4; ++w)
-        if (wv[w][0] > best || (wv[w][0] == best && wi[w][0] < bidx)) best = wv[w][0], bidx = wi[w][0], bz = wi[w][1];
-      writer = true;
-    }
-  } else {
-    float tv[KM];
-    int ti[KM];
-#pragma unroll
-    for (int u = 0; u < KM; ++u) tv[u] = -INFINITY, ti[u] = 0x7fffffff;
-    if constexpr (NV > 0) {
-#pragma unroll
-      for (int u = 0; u < NV; ++u)
-        if (tid + 256 * u < V) topk_insert<KM>(tv, ti, xr[u], tid + 256 * u);
-    } else {
-      for (int c = tid; c < V; c += 256) topk_insert<KM>(tv, ti, x[c], c);
-    }
-    for (int sel = 0; sel < top_k; ++sel) {  // each wave's top_k best: the winner pops its list head
-      float hv = tv[0];
-      int hi = ti[0], hpos = lane;
-      wave_best(hv, hi, hpos);
-      if (lane == 0) wv[wave][sel] = hv, wi[wave][sel] = hi;
-      if (lane == hpos) {
-#pragma unroll
-        for (int u = 0; u + 1 < KM; ++u) tv[u] = tv[u + 1], ti[u] = ti[u + 1];
-        tv[KM - 1] = -INFINITY, ti[KM - 1] = 0x7fffffff;
-      }
-    }
-    __syncthreads();
-    if (wave == 0) {  // the row's top_k of the waves' 4 top_k: lane sel keeps candidate sel
-      const bool on = lane < 4 * top_k;
-      float v = on ? wv[lane / top_k][lane % top_k] : -INFINITY;
-      int c = on ? wi[lane / top_k][lane % top_k] : 0x7fffffff;
-      float cx = -INFINITY;
-      int cc = 0x7fffffff;
-      for (int sel = 0; sel < top_k; ++sel) {
-        float hv = v;
-        int hi = c, hpos = lane;
-        wave_best(hv, hi, hpos);
-        if (lane == sel) cx = hv, cc = hi;
-        if (lane == hpos) v = -INFINITY, c = 0x7fffffff;
-      }
-      const bool in_c = lane < top_k;
-      const float z = in_c ? __fmul_rn(cx, inv_tau) : -INFINITY;
-      mx = wave_max(z);
-      se = wave_sum(in_c ? expf(z - mx) : 0.f);
-      best = in_c ? z + gumbel_noise(key, base + (uint32_t)cc) : -INFINITY;
-      bidx = cc, bz = __float_as_int(z);
-      wave_best(best, bidx, bz);
-      writer = lane == 0;
-    }
-  }
-  if (writer) {
-    const int token = (unsigned)bidx < (unsigned)V ? bidx : 0;  // (a row of NaNs has no winner)
-    ids_out[(int64_t)r * ids_ld + col] = token;
-    if (next_ids) next_ids[(int64_t)r * next_ld] = token;
-    if (logp_out) logp_out[(int64_t)r * logp_ld + logp_col] = (__int_as_float(bz) - mx) - logf(se);
-  }
-}
-
-using SampleKernel = void (*)(const float*, int, float, int, uint64_t, uint32_t, int64_t*, int64_t, int, int32_t*,
-                              int64_t, float*, int64_t, int);
-template <int KM>
-static SampleKernel sample_softmax_form(int V) {
-  return V <= 256 * 40 ? sample_softmax_kernel<40, KM> : sample_softmax_kernel<0, KM>;
-}
-
-void sample_softmax(const float* logits, int R, int V, float inv_tau, int top_k, uint64_t seed, uint32_t site,
-                    int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids, int64_t next_ld, float* logp_out,
-                    int64_t logp_ld, int logp_col, hipStream_t s) {
-  require(R >= 1 && V >= 1 && (int64_t)R * V < ((int64_t)1 << 32), "sample_softmax: need R, V >= 1 and R * V < 2^32");
-  require(inv_tau > 0.f && inv_tau < INFINITY, "sample_softmax: temperature must be > 0 and finite");
-  require(top_k >= 0 && top_k <= 16 && top_k <= V, "sample_softmax: top_k must be in [0, min(16, num_vocab)]");
-  require(logits && ids_out && col >= 0 && logp_col >= 0, "sample_softmax: null logits / ids_out or a negative column");
-  const SampleKernel kern = top_k == 0   ? sample_softmax_form<0>(V)
-                            : top_k <= 4 ? sample_softmax_form<4>(V)
-                            : top_k == 5 ? sample_softmax_form<5>(V)
-                            : top_k <= 8 ? sample_softmax_form<8>(V)
-                                         : sample_softmax_form<16>(V);
-  kern<<<R, 256, 0, s>>>(logits, V, inv_tau, top_k, seed, site, ids_out, ids_ld, col, next_ids, next_ld, logp_out,
-                         logp_ld, logp_col);
-  CAPGEN_HIP(hipGetLastError());
-}
-
-// ---- nucleus (top-p) sampling: the selection above with the candidate set cut to a nucleus ----
-// One row of f32 logits [V], inv_tau, top_k, and top_p in (0, 1]:
-// - z_v = logits[v] * inv_tau, one f32 product, as sample_softmax.
-// - Base set C0: every v < V when top_k == 0.  Otherwise the top_k columns under (logit descending,
-//   v ascending), as sample_softmax.
-// - M = max over C0 of z_v, P = sum_{u in C0} exp(z_u - M), above(v) = sum_{u in C0, z_u > z_v}
-//   exp(z_u - M).  The inequality is strict.
-// - Candidate set: C = { v in C0 : above(v) < top_p * P }.  A word is kept exactly when the words
-//   strictly more likely than it do not already hold top_p of the mass.  C always holds the row's
-//   maximum and is nested in top_p.  Columns with bit-equal z are in or out together, so the set does
-//   not depend on column order (top_k may still cut a tie group by index, as sample_softmax).  With
-//   top_k > 0 the mass is the one renormalised over C0: top-k first, nucleus within it.
-// - top_p == 1 means C = C0 by definition, not by arithmetic: the launcher then launches
-//   sample_softmax_kernel itself, so tokens and log-probabilities are bit-identical to sample_softmax.
-// - Token: argmax over C of (z_v + g_v), first index on ties; g is exactly sample_softmax's noise
-//   (the same hash, counter r * V + v and site).  The draw is therefore coupled to the untruncated
-//   one: whenever the top_p = 1 winner lies in C, it is also the nucleus winner.
-// - Log-probability: logp = z_token - M_C - log sum_{v in C} exp(z_v - M_C), the log-probability
-//   under the distribution actually sampled (M_C = M, since C holds the maximum).  Exactly 0 when
-//   |C| = 1.
-// - Stores: as sample_softmax, and an optional count_out[r] = |C| (int32).  Nothing else is written.
-// top_k > 0: after sample_softmax_kernel's merge C0 sits one column per lane in wave 0; above(v) is
-// top_k lane broadcasts, summed in lane order.  top_k == 0: C is { v : key(z_v) >= k* } for the
-// order-preserving integer key of the f32 z (-0 counted as +0); k* is the smallest key with
-// mass_above(k*) < top_p * P, found by bisection of the 32-bit key range in exactly 32 steps, each one
-// fixed-order block sum (no atomics: one result per seed, bit for bit).  mass_above is a sum of
-// non-negative terms in a fixed order with some of them zeroed, so it is monotone in the key, and
-// mass_above(key(-inf)) is P bit for bit: a column whose exp underflows is never in C.  The register
-// form (NV = 40) keeps the row's keys and exponentials (80 VGPRs); the generic form recomputes them
-// from memory in every step.  Every trip count is a constant or V / 256.  A row of NaNs or infinities
-// leaves a NaN mass, every comparison false, and no winner: token 0, as sample_softmax.
-__device__ __forceinline__ uint32_t z_key(float z) {
-  const uint32_t b = (uint32_t)__float_as_int(z + 0.f);  // -0 -> +0
-  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float key_z(uint32_t k) {
-  return __int_as_float((int)(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)));
-}
-__device__ __forceinline__ int block_sum_int(int v, int* sh) {
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 4, 64);
-  v += __shfl_xor(v, 8, 64);
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const int r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return r;
-}
-
-template <int NV, int KM>
-__global__ void __launch_bounds__(256) sample_nucleus_kernel(const float* __restrict__ logits, int V, float inv_tau,
-                                                             int top_k, float top_p, uint64_t seed, uint32_t site,
-                                                             int64_t* ids_out, int64_t ids_ld, int col,
-                                                             int32_t* next_ids, int64_t next_ld, float* logp_out,
-                                                             int64_t logp_ld, int logp_col, int32_t* count_out) {
-  __shared__ float sh[4];
-  __shared__ float wv[4][16];
-  __shared__ int wi[4][16];
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* x = logits + (int64_t)r * V;
-  const uint32_t key = drop_key(seed, site), base = (uint32_t)r * (uint32_t)V;
-  // the winner's (perturbed score, column, bits of its z); M, the exp-sum over C and |C|
-  float best = -INFINITY, mx = -INFINITY, se = 0.f;
-  int bidx = 0x7fffffff, bz = 0, cnt = 0;
-  bool writer = false;
-  if constexpr (KM == 0) {
-    uint32_t kr[NV > 0 ? NV : 1];  // key(z); 0 past the row's end
-    float er[NV > 0 ? NV : 1];     // exp(z - M); 0 past the row's end
-    if constexpr (NV > 0) {
-      float xr[NV];
-#pragma unroll
-      for (int u = 0; u < NV; ++u) {
-        const int c = tid + 256 * u;
-        xr[u] = c < V ? x[c] : -INFINITY;
-      }
-#pragma unroll
-      for (int u = 0; u < NV; ++u) {
-        const float z = __fmul_rn(xr[u], inv_tau);
-        if (tid + 256 * u < V) mx = fmaxf(mx, z);
-        kr[u] = tid + 256 * u < V ? z_key(z) : 0u;
-      }
-    } else {
-      for (int c = tid; c < V; c += 256) mx = fmaxf(mx, __fmul_rn(x[c], inv_tau));
-    }
-    mx = block_max(mx, sh);
-    float pe = 0.f;
-    if constexpr (NV > 0) {
-#pragma unroll
-      for (int u = 0; u < NV; ++u) {
-        er[u] = tid + 256 * u < V ? expf(key_z(kr[u]) - mx) : 0.f;
-        pe += er[u];
-      }
-    } else {
-      for (int c = tid; c < V; c += 256) pe += expf(__fmul_rn(x[c], inv_tau) - mx);
-    }
-    const float thr = __fmul_rn(top_p, block_sum(pe, sh));  // top_p * P
-    // the mass of the columns whose key is above k: the same per-thread order and block sum as P
-    auto mass_above = [&](uint32_t k) {
-      float a = 0.f;
-      if constexpr (NV > 0) {
-#pragma unroll
-        for (int u = 0; u < NV; ++u) a += kr[u] > k ? er[u] : 0.f;
-      } else {
-        for (int c = tid; c < V; c += 256) {
-          const float z = __fmul_rn(x[c], inv_tau);
-          a += z_key(z) > k ? expf(z - mx) : 0.f;
-        }
-      }
-      return block_sum(a, sh);
-    };
-    // k* = the smallest key k with mass_above(k) < top_p * P: [lo, hi] halves exactly 32 times
-    uint32_t lo = 0u, hi = 0xFFFFFFFFu;
-    for (int it = 0; it < 32; ++it) {
-      const uint32_t mid = lo + ((hi - lo) >> 1);
-      if (mass_above(mid) < thr) hi = mid;
-      else lo = mid + 1u;
-    }
-    auto visit = [&](uint32_t kz, float e, int c) {
-      if (kz < lo) return;
-      const float z = key_z(kz);
-      se += e;
-      ++cnt;
-      const float sc = z + gumbel_noise(key, base + (uint32_t)c);
-      if (sc > best) best = sc, bidx = c, bz = __float_as_int(z);
-    };
-    if constexpr (NV > 0) {
-#pragma unroll
-      for (int u = 0; u < NV; ++u)
-        if (tid + 256 * u < V) visit(kr[u], er[u], tid + 256 * u);
-    } else {
-      for (int c = tid; c < V; c += 256) {
-        const float z = __fmul_rn(x[c], inv_tau);
-        visit(z_key(z), expf(z - mx), c);
-      }
-    }
-    se = block_sum(se, sh);
-    cnt = block_sum_int(cnt, wi[0]);
-    wave_best(best, bidx, bz);
-    if (lane == 0) wv[wave][0] = best, wi[wave][0] = bidx, wi[wave][1] = bz;
-    __syncthreads();
-    if (tid == 0) {
-      for (int w = 1; w < 4; ++w)
-        if (wv[w][0] > best || (wv[w][0] == best && wi[w][0] < bidx)) best = wv[w][0], bidx = wi[w][0], bz = wi[w][1];
-      writer = true;
-    }
-  } else {
-    float tv[KM];
-    int ti[KM];
-#pragma unroll
-    for (int u = 0; u < KM; ++u) tv[u] = -INFINITY, ti[u] = 0x7fffffff;
-    if constexpr (NV > 0) {
-      float xr[NV];
-#pragma unroll
-      for (int u = 0; u < NV; ++u) {
-        const int c = tid + 256 * u;
-        xr[u] = c < V ? x[c] : -INFINITY;
-      }
-#pragma unroll
-      for (int u = 0; u < NV; ++u)
-        if (tid + 256 * u < V) topk_insert<KM>(tv, ti, xr[u], tid + 256 * u);
-    } else {
-      for (int c = tid; c < V; c += 256) topk_insert<KM>(tv, ti, x[c], c);
-    }
-    for (int sel = 0; sel < top_k; ++sel) {  // each wave's top_k best: the winner pops its list head
-      float hv = tv[0];
-      int hi = ti[0], hpos = lane;
-      wave_best(hv, hi, hpos);
-      if (lane == 0) wv[wave][sel] = hv, wi[wave][sel] = hi;
-      if (lane == hpos) {
-#pragma unroll
-        for (int u = 0; u + 1 < KM; ++u) tv[u] = tv[u + 1], ti[u] = ti[u + 1];
-        tv[KM - 1] = -INFINITY, ti[KM - 1] = 0x7fffffff;
-      }
-    }
-    __syncthreads();
-    if (wave == 0) {  // the row's top_k of the waves' 4 top_k: lane sel keeps candidate sel
-      const bool on = lane < 4 * top_k;
-      float v = on ? wv[lane / top_k][lane % top_k] : -INFINITY;
-      int c = on ? wi[lane / top_k][lane % top_k] : 0x7fffffff;
-      float cx = -INFINITY;
-      int cc = 0x7fffffff;
-      for (int sel = 0; sel < top_k; ++sel) {
-        float hv = v;
-        int hi = c, hpos = lane;
-        wave_best(hv, hi, hpos);
-        if (lane == sel) cx = hv, cc = hi;
-        if (lane == hpos) v = -INFINITY, c = 0x7fffffff;
-      }
-      const bool in_c0 = lane < top_k;
-      const float z = in_c0 ? __fmul_rn(cx, inv_tau) : -INFINITY;
-      mx = wave_max(z);
-      const float e = in_c0 ? expf(z - mx) : 0.f;
-      // P and above(v) in one lane order, so that above(v) is P bit for bit under a column of no mass
-      float pe = 0.f, above = 0.f;
-#pragma unroll
-      for (int j = 0; j < KM; ++j) {  // lanes >= top_k hold z = -inf, e = 0
-        const float zj = __shfl(z, j, 64), ej = __shfl(e, j, 64);
-        pe += ej;
-        above += zj > z ? ej : 0.f;
-      }
-      const bool in_c = in_c0 && above < __fmul_rn(top_p, pe);
-      se = wave_sum(in_c ? e : 0.f);
-      cnt = __popcll(__ballot(in_c));
-      best = in_c ? z + gumbel_noise(key, base + (uint32_t)cc) : -INFINITY;
-      bidx = in_c ? cc : 0x7fffffff, bz = __float_as_int(z);
-      wave_best(best, bidx, bz);
-      writer = lane == 0;
-    }
-  }
-  if (writer) {
-    const int token = (unsigned)bidx < (unsigned)V ? bidx : 0;  // (a row of NaNs has no winner)
-    ids_out[(int64_t)r * ids_ld + col] = token;
-    if (next_ids) next_ids[(int64_t)r * next_ld] = token;
-    if (logp_out) logp_out[(int64_t)r * logp_ld + logp_col] = (__int_as_float(bz) - mx) - logf(se);
-    if (count_out) count_out[r] = cnt;
-  }
-}
-
-__global__ void fill_i32_kernel(int32_t* p, int n, int32_t v) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) p[i] = v;
-}
-
-using NucleusKernel = void (*)(const float*, int, float, int, float, uint64_t, uint32_t, int64_t*, int64_t, int,
-                               int32_t*, int64_t, float*, int64_t, int, int32_t*);
-template <int KM>
-static NucleusKernel sample_nucleus_form(int V) {
-  return V <= 256 * 40 ? sample_nucleus_kernel<40, KM> : sample_nucleus_kernel<0, KM>;
-}
-
-void sample_nucleus(const float* logits, int R, int V, float inv_tau, int top_k, float top_p, uint64_t seed,
-                    uint32_t site, int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids, int64_t next_ld,
-                    float* logp_out, int64_t logp_ld, int logp_col, int32_t* count_out, hipStream_t s) {
-  require(top_p > 0.f && top_p <= 1.f, "sample_nucleus: top_p must be in (0, 1]");  // (false for a NaN)
-  if (top_p == 1.f) {  // C = C0 by definition: sample_softmax's own kernels
-    sample_softmax(logits, R, V, inv_tau, top_k, seed, site, ids_out, ids_ld, col, next_ids, next_ld, logp_out, logp_ld,
-                   logp_col, s);
-    if (count_out) {
-      fill_i32_kernel<<<(R + 255) / 256, 256, 0, s>>>(count_out, R, top_k == 0 ? V : top_k);
-      CAPGEN_HIP(hipGetLastError());
-    }
-    return;
-  }
-  require(R >= 1 && V >= 1 && (int64_t)R * V < ((int64_t)1 << 32), "sample_nucleus: need R, V >= 1 and R * V < 2^32");
-  require(inv_tau > 0.f && inv_tau < INFINITY, "sample_nucleus: temperature must be > 0 and finite");
-  require(top_k >= 0 && top_k <= 16 && top_k <= V, "sample_nucleus: top_k must be in [0, min(16, num_vocab)]");
-  require(logits && ids_out && col >= 0 && logp_col >= 0, "sample_nucleus: null logits / ids_out or a negative column");
-  const NucleusKernel kern = top_k == 0   ? sample_nucleus_form<0>(V)
-                             : top_k <= 4 ? sample_nucleus_form<4>(V)
-                             : top_k == 5 ? sample_nucleus_form<5>(V)
-                             : top_k <= 8 ? sample_nucleus_form<8>(V)
-                                          : sample_nucleus_form<16>(V);
-  kern<<<R, 256, 0, s>>>(logits, V, inv_tau, top_k, top_p, seed, site, ids_out, ids_ld, col, next_ids, next_ld,
-                         logp_out, logp_ld, logp_col, count_out);
-  CAPGEN_HIP(hipGetLastError());
-}
-
-// ---- bf16 decode selection from slab stats (GemmArgs::dec_stats) ----------------------------
-// One wave per row, 4 rows per workgroup.  The row's ceil(V/16) slab stats (8 B each, 1/8 of the
-// f32 logits) sit NS per lane in registers: one pass gives the row max M and the exp-sum
-// se = sum_c s_c exp(m_c - M) (the softmax of the selected elements is exp(x - M) / se), and each
-// lane's sorted best slabs.  Any element of the row's top k (value desc, index asc) lies in one of
-// the k best slabs under (max desc, slab asc): every slab ranked before the slab of the k-th best
-// element holds, as its maximum, a distinct element ranked before it.  So only k * 16 logits are
-// read back.  (The softmax is monotone in the logit; two logits rounding to one probability could
-// order by index differently than a full scan would -- the bf16 path is held to the fp32 engine by
-// the top-2-margin tests, the fp32 parity path keeps the exact full-row kernels above.)
-constexpr int kSlabNS = 16;  // slabs per lane: V <= 64 * 16 * 16 = 16384
-bool slab_select_ok(int V) { return V >= 1 && (V + 15) / 16 <= 64 * kSlabNS; }
-
-struct SlabRow {
-  float M, se;
-};
-// the row max and exp-sum from the stats; every lane ends with both
-__device__ __forceinline__ SlabRow slab_row_stats(const float2* __restrict__ st, int S, int lane, float (&mx)[kSlabNS]) {
-  float2 x[kSlabNS];
-  float M = -INFINITY;
-#pragma unroll
-  for (int u = 0; u < kSlabNS; ++u) {
-    const int c = lane + 64 * u;
-    x[u] = c < S ? st[c] : float2{-INFINITY, 0.f};
-    mx[u] = x[u].x;
-    M = fmaxf(M, x[u].x);
-  }
-  M = wave_max(M);
-  float se = 0.f;
-#pragma unroll
-  for (int u = 0; u < kSlabNS; ++u)
-    if (lane + 64 * u < S) se += x[u].y * __expf(x[u].x - M);
-  return SlabRow{M, wave_sum(se)};
-}
-
-__global__ void __launch_bounds__(256) slab_argmax_kernel(const float* __restrict__ logits,
-                                                          const float2* __restrict__ stats, int B, int V,
-                                                          int64_t* __restrict__ ids_out, int64_t ids_ld, int col,
-                                                          int32_t* __restrict__ next_ids, int64_t next_ld) {
-  const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (b >= B) return;  // (whole waves)
-  const int S = (V + 15) / 16;
-  const float2* st = stats + (int64_t)b * S;
-  // best slab of this lane (max desc, slab asc), then of the wave
-  float best = -INFINITY;
-  int bidx = 0x7fffffff, bpos = lane;
-#pragma unroll
-  for (int u = 0; u < kSlabNS; ++u) {
-    const int c = lane + 64 * u;
-    if (c < S) {
-      const float m = st[c].x;
-      if (m > best) best = m, bidx = c;  // c ascends: ties keep the first
-    }
-  }
-  wave_best(best, bidx, bpos);
-  // the slab's 16 logits: the first column holding the maximum
-  const int c = bidx * 16 + lane;
-  float v = -INFINITY;
-  int vi = 0x7fffffff, vp = lane;
-  if (lane < 16 && c < V) v = logits[(int64_t)b * V + c], vi = c;
-  wave_best(v, vi, vp);
-  if (lane == 0) {
-    ids_out[(int64_t)b * ids_ld + col] = vi;
-    if (next_ids) next_ids[(int64_t)b * next_ld] = vi;
-  }
-}
-void slab_argmax(const float* logits, const float2* stats, int B, int V, int64_t* ids_out, int64_t ids_ld, int col,
-                 int32_t* next_ids, int64_t next_ld, hipStream_t s) {
-  require(slab_select_ok(V), "slab_argmax: V must be in [1, 16384]");
-  slab_argmax_kernel<<<(B + 3) / 4, 256, 0, s>>>(logits, stats, B, V, ids_out, ids_ld, col, next_ids, next_ld);
-  CAPGEN_HIP(hipGetLastError());
-}
-
-// one row's k best (value desc, index asc) from its slab stats: a wave per row, lane 0 leaves them in
-// (out_v, out_i)[0 .. k); chosen = this wave's KM-entry LDS scratch (row j = beam index)
-template <int KM>
-__device__ __forceinline__ void slab_row_topk_wave(const float* __restrict__ logits, const float2* __restrict__ stats,
-                                                   const float* __restrict__ prev, int r, int j, int V, int k,
-                                                   int logsm, int* chosen, int lane, float* out_v, int* out_i) {
-  const int S = (V + 15) / 16;
-  float mx[kSlabNS];
-  const SlabRow rs = slab_row_stats(stats + (int64_t)r * S, S, lane, mx);
-  // each lane's best KM slabs, sorted; then k wave rounds pick the row's k best slabs
-  float tv[KM];
-  int ti[KM];
-#pragma unroll
-  for (int u = 0; u < KM; ++u) tv[u] = -INFINITY, ti[u] = 0x7fffffff;
-#pragma unroll
-  for (int u = 0; u < kSlabNS; ++u) {
-    const int c = lane + 64 * u;
-    if (c < S) topk_insert<KM>(tv, ti, mx[u], c);
-  }
-  for (int sel = 0; sel < k; ++sel) {
-    float best = tv[0];
-    int bidx = ti[0], bpos = lane;
-    wave_best(best, bidx, bpos);
-    if (lane == 0) chosen[sel] = bidx;  // (0x7fffffff when S < k: no such slab)
-    if (lane == bpos) {
-#pragma unroll
-      for (int u = 0; u + 1 < KM; ++u) tv[u] = tv[u + 1], ti[u] = ti[u + 1];
-      tv[KM - 1] = -INFINITY, ti[KM - 1] = 0x7fffffff;
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // lane 0's LDS writes before the reads below
-  // the k * 16 candidate logits, scored exactly as the full-row kernel scores them
-  const float lse = __logf(rs.se), add = prev ? prev[r] : 0.f;
-#pragma unroll
-  for (int u = 0; u < KM; ++u) tv[u] = -INFINITY, ti[u] = 0x7fffffff;
-  const float* x = logits + (int64_t)r * V;
-  for (int e = lane; e < k * 16; e += 64) {
-    const int sl = chosen[e >> 4];
-    if (sl == 0x7fffffff) continue;
-    const int c = sl * 16 + (e & 15);
-    if (c >= V) continue;
-    const float xv = x[c];
-    topk_insert<KM>(tv, ti, (logsm ? (xv - rs.M) - lse : __expf(xv - rs.M) / rs.se) + add, j * V + c);
-  }
-  for (int sel = 0; sel < k; ++sel) {
-    float best = tv[0];
-    int bidx = ti[0], bpos = lane;
-    wave_best(best, bidx, bpos);
-    if (lane == 0) out_v[sel] = best, out_i[sel] = bidx;
-    if (lane == bpos) {
-#pragma unroll
-      for (int u = 0; u + 1 < KM; ++u) tv[u] = tv[u + 1], ti[u] = ti[u + 1];
-      tv[KM - 1] = -INFINITY, ti[KM - 1] = 0x7fffffff;
-    }
-  }
-}
-
-template <int KM>
-__global__ void __launch_bounds__(256) slab_row_topk_kernel(const float* __restrict__ logits,
-                                                            const float2* __restrict__ stats,
-                                                            const float* __restrict__ prev, int rows, int B, int V,
-                                                            int k, int logsm, float* __restrict__ cand_v,
-                                                            int* __restrict__ cand_i) {
-  __shared__ int chosen[4][KM];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = blockIdx.x * 4 + wave;
-  if (r >= rows) return;  // (whole waves; no workgroup barrier below)
-  slab_row_topk_wave<KM>(logits, stats, prev, r, r / B, V, k, logsm, chosen[wave], lane, cand_v + (int64_t)r * k,
-                         cand_i + (int64_t)r * k);
-}
-
-// The whole beam step of one image in ONE workgroup (round 6): wave j takes beam row j * B + i's k best
-// (slab_row_topk_wave) into LDS, wave 0 merges the k_in * k finalists exactly as beam_merge_kernel, and
-// every thread then moves the image's k new rows -- sequences and ids gathered from their source beams
-// with the chosen token at column t + 1, and the beam K/V row table (model.py:186-198) -- which took
-// four more launches (merge, two gathers, the row table) per token.
-template <int KM>
-__global__ void __launch_bounds__(1024) beam_slab_step_kernel(
-    const float* __restrict__ logits, const float2* __restrict__ stats, const float* __restrict__ prev, int k_in,
-    int B, int V, int k, int logsm, float* __restrict__ out_prob, int32_t* __restrict__ out_src,
-    int32_t* __restrict__ out_tok, const int64_t* __restrict__ seq_src, int64_t* __restrict__ seq_dst, int Tw,
-    const int32_t* __restrict__ ids_src, int32_t* __restrict__ ids_dst, const int32_t* __restrict__ kv_src,
-    int32_t* __restrict__ kv_dst, int Tc, int t) {
-  __shared__ int chosen[16][KM];
-  __shared__ float cv[256];
-  __shared__ int ci[256];
-  __shared__ int bsrc[16], btok[16];
-  const int i = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (wave < k_in)
-    slab_row_topk_wave<KM>(logits, stats, prev, wave * B + i, wave, V, k, logsm, chosen[wave], lane, cv + wave * k,
-                           ci + wave * k);
-  __syncthreads();
-  if (wave == 0) {  // beam_merge_kernel over the LDS finalists (entry e = row e / k, rank e % k)
-    const int n = k_in * k;
-    float v[4];
-    int c[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int e = lane + 64 * u;
-      const bool on = e < n;
-      v[u] = on ? cv[e] : -INFINITY;
-      c[u] = on ? ci[e] : 0x7fffffff;
-    }
-    for (int sel = 0; sel < k; ++sel) {
-      float best = -INFINITY;
-      int bidx = 0x7fffffff, bpos = -1;
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (v[u] > best || (v[u] == best && c[u] < bidx)) best = v[u], bidx = c[u], bpos = lane + 64 * u;
-      wave_best(best, bidx, bpos);
-      if (lane == 0) {
-        out_prob[sel * B + i] = best;
-        out_src[sel * B + i] = bsrc[sel] = bidx / V;
-        out_tok[sel * B + i] = btok[sel] = bidx % V;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (bpos == lane + 64 * u) v[u] = -INFINITY, c[u] = 0x7fffffff;
-    }
-  }
-  __syncthreads();
-  // the image's k new rows r = j * B + i from their source rows bsrc[j] * B + i (double-buffered arrays)
-  for (int e = threadIdx.x; e < k * (Tw + 2 * Tc); e += blockDim.x) {
-    const int j = e / (Tw + 2 * Tc), q = e % (Tw + 2 * Tc);
-    const int64_t r = (int64_t)j * B + i, srow = (int64_t)bsrc[j] * B + i;
-    if (q < Tw) {
-      seq_dst[r * Tw + q] = q == t + 1 ? (int64_t)btok[j] : seq_src[srow * Tw + q];
-    } else if (q < Tw + Tc) {
-      const int cc = q - Tw;
-      ids_dst[r * Tc + cc] = cc == t + 1 ? btok[j] : ids_src[srow * Tc + cc];
-    } else {
-      const int cc = q - Tw - Tc;
-      kv_dst[r * Tc + cc] = cc <= t ? kv_src[srow * Tc + cc] : (cc == t + 1 ? (int32_t)r : 0);
-    }
-  }
-}
-
-void beam_slab_step(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
-                    int logsm, float* out_prob, int32_t* out_src, int32_t* out_tok, const int64_t* seq_src,
-                    int64_t* seq_dst, int Tw, const int32_t* ids_src, int32_t* ids_dst, const int32_t* kv_src,
-                    int32_t* kv_dst, int Tc, int t, hipStream_t s) {
-  require(k >= 1 && k <= 16 && k_in >= 1 && k_in <= 16 && k_in * k <= 256, "beam_slab_step: k, k_in in [1, 16]");
-  require(slab_select_ok(V) && t + 1 < Tw && t + 1 < Tc, "beam_slab_step: V in [1, 16384], t + 1 < width");
-  if (hz::active()) {
-    using namespace hz;
-    const int R = k * B, S = (V + 15) / 16;
-    op(s, "beam_slab_step", {rd(logits, (int64_t)k_in * B * V * 4), rd(stats, (int64_t)k_in * B * S * 8),
-                             rd(prev, prev ? (int64_t)k_in * B * 4 : 0), wr(out_prob, (int64_t)k * B * 4),
-                             wr(out_src, (int64_t)k * B * 4), wr(out_tok, (int64_t)k * B * 4),
-                             rd(seq_src, (int64_t)R * Tw * 8), wr(seq_dst, (int64_t)R * Tw * 8),
-                             rd(ids_src, (int64_t)R * Tc * 4), wr(ids_dst, (int64_t)R * Tc * 4),
-                             rd(kv_src, (int64_t)R * Tc * 4), wr(kv_dst, (int64_t)R * Tc * 4)});
-  }
-  const int nt = 64 * k_in;
-  auto go = [&](auto km) {
-    beam_slab_step_kernel<decltype(km)::value><<<B, nt, 0, s>>>(logits, stats, prev, k_in, B, V, k, logsm, out_prob,
-                                                                out_src, out_tok, seq_src, seq_dst, Tw, ids_src,
-                                                                ids_dst, kv_src, kv_dst, Tc, t);
-  };
-  if (k <= 4) go(std::integral_constant<int, 4>{});
-  else if (k == 5) go(std::integral_constant<int, 5>{});
-  else if (k <= 8) go(std::integral_constant<int, 8>{});
-  else go(std::integral_constant<int, 16>{});
-  CAPGEN_HIP(hipGetLastError());
-}
-
-void beam_step_topk_slab(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
-                         int logsm, float* cand_v, int32_t* cand_i, float* out_prob, int32_t* out_src,
-                         int32_t* out_tok, hipStream_t s) {
-  require(k >= 1 && k <= 16 && k_in >= 1 && k_in * k <= 256, "beam_step_topk_slab: k in [1, 16]");
-  require(slab_select_ok(V), "beam_step_topk_slab: V must be in [1, 16384]");
-  const int rows = k_in * B, grid = (rows + 3) / 4;
-  if (k <= 4) slab_row_topk_kernel<4><<<grid, 256, 0, s>>>(logits, stats, prev, rows, B, V, k, logsm, cand_v, cand_i);
-  else if (k == 5) slab_row_topk_kernel<5><<<grid, 256, 0, s>>>(logits, stats, prev, rows, B, V, k, logsm, cand_v, cand_i);
-  else if (k <= 8) slab_row_topk_kernel<8><<<grid, 256, 0, s>>>(logits, stats, prev, rows, B, V, k, logsm, cand_v, cand_i);
-  else slab_row_topk_kernel<16><<<grid, 256, 0, s>>>(logits, stats, prev, rows, B, V, k, logsm, cand_v, cand_i);
-  beam_merge_kernel<<<B, 64, 0, s>>>(cand_v, cand_i, k_in, B, V, k, out_prob, out_src, out_tok);
   CAPGEN_HIP(hipGetLastError());
 }
 

@@ -11,27 +11,9 @@
 //           a = (1-w)/count [tgt != pad], c = w score_b mask_bt / sum(mask)
 // All-reduced scalars (DP): count (forward), sum(mask) and the struct numerator (rl_finish).
 #include "rl.h"
+#include "select_dev.h"  // block reductions, block_best
 
 namespace capgen {
-
-namespace {
-__device__ __forceinline__ float bmax(float v, float* sh) {
-  v = wave_max(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float r = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ float bsum(float v, float* sh) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return r;
-}
-}  // namespace
 
 __global__ void __launch_bounds__(256) rl_rows_kernel(const float* __restrict__ logits, int V,
                                                       int32_t* __restrict__ sample, float* __restrict__ lse,
@@ -43,15 +25,15 @@ __global__ void __launch_bounds__(256) rl_rows_kernel(const float* __restrict__ 
   const float* x = logits + (int64_t)m * V;
   float mx = -INFINITY;
   for (int c = threadIdx.x; c < V; c += 256) mx = fmaxf(mx, x[c]);
-  mx = bmax(mx, sh);
+  mx = block_max(mx, sh);
   float se = 0.f, sx = 0.f;
   for (int c = threadIdx.x; c < V; c += 256) {
     const float e = expf(x[c] - mx);
     se += e;
     sx = fmaf(e, x[c] - mx, sx);
   }
-  se = bsum(se, sh);
-  sx = bsum(sx, sh);
+  se = block_sum_pairwise(se, sh);
+  sx = block_sum_pairwise(sx, sh);
   const float lz = logf(se);
   // argmax of log_softmax = (x - max) - log(sum), first index on ties (torch.argmax)
   float best = -INFINITY;
@@ -60,18 +42,7 @@ __global__ void __launch_bounds__(256) rl_rows_kernel(const float* __restrict__ 
     const float lp = (x[c] - mx) - lz;
     if (lp > best) best = lp, bidx = c;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bidx, o, 64);
-    if (ov > best || (ov == best && oi < bidx)) best = ov, bidx = oi;
-  }
-  if ((threadIdx.x & 63) == 0) bv[threadIdx.x >> 6] = best, bi[threadIdx.x >> 6] = bidx;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    best = bv[0], bidx = bi[0];
-    for (int w = 1; w < 4; ++w)
-      if (bv[w] > best || (bv[w] == best && bi[w] < bidx)) best = bv[w], bidx = bi[w];
+  if (block_best(best, bidx, bv, bi)) {
     sample[m] = bidx;
     lse[m] = mx + lz;
     logp_s[m] = best;
@@ -95,7 +66,7 @@ __global__ void __launch_bounds__(256) rl_image_kernel(const int32_t* __restrict
     ent_img[b] = es / ms;
     msum += ms;
   }
-  msum = bsum(msum, sh);
+  msum = block_sum_pairwise(msum, sh);
   if (threadIdx.x == 0) scal[0] = msum;
 }
 
@@ -111,7 +82,7 @@ __global__ void __launch_bounds__(256) rl_numer_kernel(const int32_t* __restrict
     const float mk = (t == 0 || sample[m - 1] > 0) ? 1.f : 0.f;
     acc = fmaf(-logp_s[m] * mk, score[b], acc);
   }
-  acc = bsum(acc, sh);
+  acc = block_sum_pairwise(acc, sh);
   if (threadIdx.x == 0) scal[1] = acc;
 }
 

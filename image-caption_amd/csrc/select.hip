@@ -1,0 +1,706 @@
+// capgen — decode selection kernels for gfx950: what turns a decode step's logits into tokens.
+//
+// Greedy argmax, the beam step's per-row top-k and per-image merge, temperature / top-k / nucleus
+// sampling by Gumbel-max, the bf16 path's selection from the classifier's slab stats, and the beam
+// bookkeeping of the generation loops.  Every selection orders candidates by (value descending, index
+// ascending).  The pieces the kernels are built from -- the row in registers, the sorted per-thread
+// lists and the wave rounds over them, the block winner and the block reductions -- are in select_dev.h.
+#include <algorithm>
+#include <type_traits>
+
+#include "select.h"
+#include "select_dev.h"
+#include "hazard.h"
+
+namespace capgen {
+
+// k -> the per-thread list length KM in {4, 5, 8, 16} the selection kernels are built for (k <= 16):
+// calls f(std::integral_constant<int, KM>)
+template <class F>
+static void with_km(int k, F&& f) {
+  if (k <= 4) f(std::integral_constant<int, 4>{});
+  else if (k == 5) f(std::integral_constant<int, 5>{});
+  else if (k <= 8) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 16>{});
+}
+
+// ---- greedy / beam helpers ---------------------------------------------------------
+// logsm = 0: argmax of Softmax (Transformer, model.py:124-128); 1: of LogSoftmax
+// (PolicyNetwork, model_RL.py:72,126-127) -- the same token except where the rounding of the
+// two scores makes different near-ties
+// NV > 0: the row (V <= 256 NV) is held in registers (RowRegs); the same per-thread order as NV = 0
+template <int NV>
+__global__ void __launch_bounds__(256) argmax_softmax_kernel(const float* __restrict__ logits, int V,
+                                                             int64_t* ids_out, int64_t ids_ld, int col,
+                                                             int32_t* next_ids, int64_t next_ld, int logsm) {
+  __shared__ float sh[4];
+  __shared__ float bv[4];
+  __shared__ int bi[4];
+  const int b = blockIdx.x;
+  RowRegs<NV, 256> row(logits + (int64_t)b * V, V, threadIdx.x);
+  float mx = -INFINITY;
+  row.each([&](float xv, int, int) { mx = fmaxf(mx, xv); });
+  mx = block_max(mx, sh);
+  float se = 0.f;
+  row.each([&](float xv, int, int) { se += expf(xv - mx); });
+  se = block_sum_pairwise(se, sh);
+  // argmax over the softmax probabilities, first index on ties (torch.argmax)
+  float best = -INFINITY;
+  int bidx = 0x7fffffff;
+  const float lse = logf(se);
+  row.each([&](float xv, int c, int) {
+    const float p = logsm ? (xv - mx) - lse : expf(xv - mx) / se;
+    if (p > best) {
+      best = p;
+      bidx = c;
+    }
+  });
+  if (block_best(best, bidx, bv, bi)) {
+    ids_out[(int64_t)b * ids_ld + col] = bidx;
+    if (next_ids) next_ids[(int64_t)b * next_ld] = bidx;
+  }
+}
+void argmax_softmax(const float* logits, int B, int V, int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids,
+                    int64_t next_ld, hipStream_t s, int logsm) {
+  if (V <= 256 * 40) argmax_softmax_kernel<40><<<B, 256, 0, s>>>(logits, V, ids_out, ids_ld, col, next_ids, next_ld, logsm);
+  else argmax_softmax_kernel<0><<<B, 256, 0, s>>>(logits, V, ids_out, ids_ld, col, next_ids, next_ld, logsm);
+  CAPGEN_HIP(hipGetLastError());
+}
+
+// ---- beam search step (model.py:183-190; PolicyNetwork model_RL.py:182-190 with logsm) ----
+// Candidate (j, v) of image i scores prev[j][i] + p[j*B+i][v] (p: Softmax, or LogSoftmax with
+// logsm); the k best under (score desc, flat index j*V + v asc) -- a strict total order, so the
+// selection equals a full sort's first k.  Part 1, one workgroup per decoder row r = j*B + i:
+// the row's softmax exactly as a separate softmax pass would compute it (same strided
+// per-thread order and block reductions: the scores are bit-identical), the row held in
+// registers (NV values per thread; NV = 0 re-reads it from memory), each thread's sorted
+// top-KM, and the row's top k.  Part 2, one wave per image: top k of its k_in rows' k
+// finalists each -- every image-level winner is in its row's top k.  Neither the [R, V]
+// probabilities nor a [B, k*V] scan exist: one read of the logits per step.
+
+// NT threads per row (W = NT / 64 waves), NV values per thread in registers (V <= NT * NV)
+template <int KM, int NV, int NT = 256>
+__global__ void __launch_bounds__(NT) beam_row_topk_kernel(const float* __restrict__ logits,
+                                                            const float* __restrict__ prev, int B, int V, int k,
+                                                            int logsm, float* __restrict__ cand_v,
+                                                            int* __restrict__ cand_i) {
+  constexpr int W = NT / 64;
+  __shared__ float sh[W];
+  __shared__ float wv[W][16];
+  __shared__ int wi[W][16];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = r / B;
+  RowRegs<NV, NT> row(logits + (int64_t)r * V, V, tid);
+  float mx = -INFINITY;
+  row.each([&](float xv, int, int) { mx = fmaxf(mx, xv); });
+  mx = block_max<W>(mx, sh);
+  float se = 0.f;
+  row.each([&](float& xv, int, int) {
+    const float e = expf(xv - mx);
+    se += e;
+    if (NV > 0 && !logsm) xv = e;  // Softmax scores need only exp(x - max)
+  });
+  se = block_sum_inorder<W>(se, sh);
+  const float lse = logf(se), add = prev ? prev[r] : 0.f;
+  float tv[KM];
+  int ti[KM];
+  topk_clear<KM>(tv, ti);
+  row.each([&](float xv, int c, int) {
+    const float p = logsm ? (xv - mx) - lse : (NV > 0 ? xv : expf(xv - mx)) / se;
+    topk_insert<KM>(tv, ti, p + add, j * V + c);
+  });
+  // the row's k best: each wave's k best, then wave 0 selects the row's k from the W k of them
+  wave_topk_rounds<KM>(tv, ti, k, lane, [&](int sel, float v, int i) {
+    if (lane == 0) wv[wave][sel] = v, wi[wave][sel] = i;
+  });
+  __syncthreads();
+  if (wave == 0)
+    wave_merge_finalists<W>(wv, wi, k, lane, [&](int sel, float v, int i) {
+      if (lane == 0) cand_v[(int64_t)r * k + sel] = v, cand_i[(int64_t)r * k + sel] = i;
+    });
+}
+
+// One wave, one image: the k best of its n = k_in * k row finalists (n <= 256; entry e = (row j = e / k,
+// rank e % k)).  load(e, v, c) reads entry e; emit(sel, score, flat index) runs in lane 0.
+template <class Load, class Emit>
+__device__ __forceinline__ void beam_merge_wave(int n, int k, int lane, Load&& load, Emit&& emit) {
+  float v[4];
+  int c[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    v[u] = -INFINITY, c[u] = 0x7fffffff;
+    if (lane + 64 * u < n) load(lane + 64 * u, v[u], c[u]);
+  }
+  for (int sel = 0; sel < k; ++sel) {
+    float best = -INFINITY;
+    int bidx = 0x7fffffff, bpos = -1;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (v[u] > best || (v[u] == best && c[u] < bidx)) best = v[u], bidx = c[u], bpos = lane + 64 * u;
+    wave_best(best, bidx, bpos);
+    if (lane == 0) emit(sel, best, bidx);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (bpos == lane + 64 * u) v[u] = -INFINITY, c[u] = 0x7fffffff;
+  }
+}
+
+// one wave per image over the rows' finalists in cand_v / cand_i [k_in * B][k]
+__global__ void __launch_bounds__(64) beam_merge_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
+                                                        int k_in, int B, int V, int k, float* __restrict__ out_prob,
+                                                        int32_t* __restrict__ out_src, int32_t* __restrict__ out_tok) {
+  const int i = blockIdx.x;
+  beam_merge_wave(
+      k_in * k, k, threadIdx.x,
+      [&](int e, float& v, int& c) {
+        const int64_t src = ((int64_t)(e / k) * B + i) * k + e % k;
+        v = cand_v[src], c = cand_i[src];
+      },
+      [&](int sel, float best, int bidx) {
+        out_prob[sel * B + i] = best;
+        out_src[sel * B + i] = bidx / V;
+        out_tok[sel * B + i] = bidx % V;
+      });
+}
+
+template <int KM>
+static void beam_row_topk(const float* logits, const float* prev, int rows, int B, int V, int k, int logsm,
+                          float* cand_v, int32_t* cand_i, hipStream_t s) {
+  // 512 threads per row where the row fits 20 values per thread (42 vs 50 us per token at B = 1280
+  // with 256 threads, round 2)
+  if (V <= 512 * 20 && KM * 8 <= 64)
+    beam_row_topk_kernel<KM, 20, 512><<<rows, 512, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i);
+  else if (V <= 256 * 40) beam_row_topk_kernel<KM, 40><<<rows, 256, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i);
+  else beam_row_topk_kernel<KM, 0><<<rows, 256, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i);
+}
+
+void beam_step_topk(const float* logits, const float* prev, int k_in, int B, int V, int k, int logsm, float* cand_v,
+                    int32_t* cand_i, float* out_prob, int32_t* out_src, int32_t* out_tok, hipStream_t s) {
+  require(k >= 1 && k <= 16 && k_in >= 1 && k_in * k <= 256, "beam_step_topk: k in [1, 16]");
+  with_km(k, [&](auto km) {
+    beam_row_topk<decltype(km)::value>(logits, prev, k_in * B, B, V, k, logsm, cand_v, cand_i, s);
+  });
+  beam_merge_kernel<<<B, 64, 0, s>>>(cand_v, cand_i, k_in, B, V, k, out_prob, out_src, out_tok);
+  CAPGEN_HIP(hipGetLastError());
+}
+
+// ---- sampled decoding: temperature / top-k / nucleus sampling by Gumbel-max, with the log-probability ----
+// One launch per decode position, one 256-thread workgroup per row r of logits [R][V] (f32); one kernel
+// template, the lines marked [nucleus] hold for NUCLEUS = true (sample_nucleus with top_p < 1) only:
+// - Scaled logits.  z_v = logits[r][v] * inv_tau (one f32 product), with inv_tau = 1 / temperature.
+// - Base set C0.  Every v < V when top_k == 0.  Otherwise the top_k columns of the row under
+//   (logit descending, v ascending), with 1 <= top_k <= min(16, V).
+// - Candidate set C.  C = C0, or
+//   [nucleus] C = { v in C0 : above(v) < top_p * P }, with M = max over C0 of z_v, P = sum_{u in C0}
+//   exp(z_u - M) and above(v) = sum_{u in C0, z_u > z_v} exp(z_u - M); the inequality is strict and top_p
+//   lies in (0, 1).  A word is kept exactly when the words strictly more likely than it do not already
+//   hold top_p of the mass.  C always holds the row's maximum and is nested in top_p.  Columns with
+//   bit-equal z are in or out together, so the set does not depend on column order (top_k may still cut
+//   a tie group by index).  With top_k > 0 the mass is the one renormalised over C0: top-k first, nucleus
+//   within it.
+//   [nucleus] top_p == 1 means C = C0 by definition, not by arithmetic: the launcher then launches the
+//   NUCLEUS = false kernel itself, so tokens and log-probabilities are bit-identical to sample_softmax.
+// - Noise.  h = mix32(seed, site, (uint32_t)(r * V + v)), then u = ((h >> 9) + 0.5f) * 2^-23, then
+//   g = -logf(-logf(u)).  u is exact in f32 and lies strictly inside (0, 1).  logf, not the __logf
+//   intrinsic: the winning column usually has u close to 1, where -log u is 1e-4 ... 6e-8, and the
+//   intrinsic's absolute error is of that size.  r is the row index within the launch; the launcher
+//   requires R * V < 2^32.
+// - Token.  token = argmax over v in C of (z_v + g_v), first index on ties.  With top_k == 1 this is
+//   the argmax of the logits, first index on ties.  A row of NaNs has no winner: token 0.
+//   [nucleus] The noise does not depend on top_p, so the draw is coupled to the untruncated one:
+//   whenever the top_p = 1 winner lies in C, it is also the nucleus winner.
+// - Log-probability.  logp = z_token - M - log sum_{v in C} exp(z_v - M), with M = max over C of z_v
+//   (= max over C0, since C holds the maximum): the log-probability under the distribution actually
+//   sampled.  Exactly 0 when |C| = 1.
+// - Stores.  ids_out[r * ids_ld + col] = token (int64); next_ids[r * next_ld] = token (int32,
+//   optional); logp_out[r * logp_ld + logp_col] = logp (optional);
+//   [nucleus] count_out[r] = |C| (int32, optional).  Nothing else is written.
+// Gumbel-max rather than an inverse-CDF scan: one pass, a result that does not depend on the
+// summation order, and an index a float64 restatement predicts exactly wherever the two best
+// perturbed scores are not within rounding of each other.  The slab statistics of the bf16 greedy /
+// beam selection are not used: their per-slab exp-sums hold at temperature 1 only.
+// NV > 0: the row (V <= 256 NV) is held in registers (as argmax_softmax_kernel).
+// KM > 0 (top_k <= KM): C0 is found as beam_row_topk_kernel finds a row's k best, wave 0 ending with one
+// column of C0 per lane.  [nucleus] above(v) is then top_k lane broadcasts, summed in lane order.
+// KM = 0 (top_k == 0): one pass for M and the Gumbel winner, a second for the exp-sum.
+// [nucleus] KM = 0: C is { v : key(z_v) >= k* } for the order-preserving integer key of the f32 z
+// (-0 counted as +0); k* is the smallest key with mass_above(k*) < top_p * P, found by bisection of the
+// 32-bit key range in exactly 32 steps, each one fixed-order block sum (no atomics: one result per seed,
+// bit for bit).  mass_above is a sum of non-negative terms in a fixed order with some of them zeroed, so
+// it is monotone in the key, and mass_above(key(-inf)) is P bit for bit: a column whose exp underflows is
+// never in C.  The register form (NV = 40) keeps the row's keys and exponentials (80 VGPRs); the generic
+// form recomputes them from memory in every step.  Every trip count is a constant or V / 256.  A row of
+// NaNs or infinities leaves a NaN mass, every comparison false, and no winner: token 0.
+__device__ __forceinline__ float gumbel_noise(uint32_t key, uint32_t idx) {
+  const uint32_t h = lowbias32(idx ^ key);  // mix32(seed, site, idx), the key hoisted
+  const float u = ((float)(h >> 9) + 0.5f) * 0x1p-23f;
+  return -logf(-logf(u));
+}
+__device__ __forceinline__ uint32_t z_key(float z) {
+  const uint32_t b = (uint32_t)__float_as_int(z + 0.f);  // -0 -> +0
+  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float key_z(uint32_t k) {
+  return __int_as_float((int)(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)));
+}
+
+// where a row's token, next decoder input and log-probability go
+struct SampleOut {
+  int64_t* ids;
+  int64_t ids_ld;
+  int col;
+  int32_t* next_ids;
+  int64_t next_ld;
+  float* logp;
+  int64_t logp_ld;
+  int logp_col;
+};
+// the winner (column bidx, scaled logit z) of row r under the candidates' max mx and exp-sum se
+__device__ __forceinline__ void write_sample(const SampleOut& o, int r, int V, int bidx, float z, float mx, float se) {
+  const int token = (unsigned)bidx < (unsigned)V ? bidx : 0;  // (a row of NaNs has no winner)
+  o.ids[(int64_t)r * o.ids_ld + o.col] = token;
+  if (o.next_ids) o.next_ids[(int64_t)r * o.next_ld] = token;
+  if (o.logp) o.logp[(int64_t)r * o.logp_ld + o.logp_col] = (z - mx) - logf(se);
+}
+
+// (top_p and count_out are read by the NUCLEUS form only)
+template <int NV, int KM, bool NUCLEUS>
+__global__ void __launch_bounds__(256) sample_kernel(const float* __restrict__ logits, int V, float inv_tau, int top_k,
+                                                     float top_p, uint64_t seed, uint32_t site, SampleOut out,
+                                                     int32_t* count_out) {
+  __shared__ float sh[4];
+  __shared__ float wv[4][16];
+  __shared__ int wi[4][16];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t key = drop_key(seed, site), base = (uint32_t)r * (uint32_t)V;
+  RowRegs<NV, 256> row(logits + (int64_t)r * V, V, tid);
+  // the winner's (perturbed score, column, bits of its z); M, the exp-sum over C and |C|
+  float best = -INFINITY, mx = -INFINITY, se = 0.f;
+  int bidx = 0x7fffffff, bz = 0, cnt = 0;
+  bool writer = false;
+  auto offer = [&](float z, int c) {
+    const float sc = z + gumbel_noise(key, base + (uint32_t)c);
+    if (sc > best) best = sc, bidx = c, bz = __float_as_int(z);
+  };
+  if constexpr (KM == 0 && !NUCLEUS) {
+    row.each([&](float xv, int c, int) {
+      const float z = __fmul_rn(xv, inv_tau);  // (not contracted into the add: z is an f32)
+      mx = fmaxf(mx, z);
+      offer(z, c);
+    });
+    mx = block_max(mx, sh);
+    row.each([&](float xv, int, int) { se += expf(__fmul_rn(xv, inv_tau) - mx); });
+    se = block_sum_pairwise(se, sh);
+    writer = block_best(best, bidx, bz, wv[0], wi[0]);
+  } else if constexpr (KM == 0) {
+    uint32_t kr[NV > 0 ? NV : 1];  // NV > 0: key(z) of the thread's columns; 0 past the row's end
+    float er[NV > 0 ? NV : 1];     // NV > 0: exp(z - M) of the thread's columns; 0 past the row's end
+    row.each_slot([&](float xv, int c, int u) {
+      const float z = __fmul_rn(xv, inv_tau);
+      mx = fmaxf(mx, z);  // (-inf past the row's end)
+      if constexpr (NV > 0) kr[u] = c < V ? z_key(z) : 0u, er[u] = 0.f;
+    });
+    mx = block_max(mx, sh);
+    float pe = 0.f;
+    row.each([&](float xv, int, int u) {
+      float z;
+      if constexpr (NV > 0) z = key_z(kr[u]);
+      else z = __fmul_rn(xv, inv_tau);
+      const float e = expf(z - mx);
+      if constexpr (NV > 0) er[u] = e;
+      pe += e;
+    });
+    const float thr = __fmul_rn(top_p, block_sum_pairwise(pe, sh));  // top_p * P
+    // a column's (key(z), exp(z - M)): kept in registers, or recomputed from the logit
+    auto key_exp = [&](float xv, int u, uint32_t& kz, float& e) {
+      if constexpr (NV > 0) {
+        kz = kr[u], e = er[u];
+      } else {
+        const float z = __fmul_rn(xv, inv_tau);
+        kz = z_key(z), e = expf(z - mx);
+      }
+    };
+    // the mass of the columns whose key is above k: the same per-thread order and block sum as P
+    auto mass_above = [&](uint32_t k) {
+      float a = 0.f;
+      row.each_slot([&](float xv, int, int u) {
+        uint32_t kz;
+        float e;
+        key_exp(xv, u, kz, e);
+        a += kz > k ? e : 0.f;
+      });
+      return block_sum_pairwise(a, sh);
+    };
+    // k* = the smallest key k with mass_above(k) < top_p * P: [lo, hi] halves exactly 32 times
+    uint32_t lo = 0u, hi = 0xFFFFFFFFu;
+    for (int it = 0; it < 32; ++it) {
+      const uint32_t mid = lo + ((hi - lo) >> 1);
+      if (mass_above(mid) < thr) hi = mid;
+      else lo = mid + 1u;
+    }
+    row.each([&](float xv, int c, int u) {
+      uint32_t kz;
+      float e;
+      key_exp(xv, u, kz, e);
+      if (kz < lo) return;
+      se += e;
+      ++cnt;
+      offer(key_z(kz), c);
+    });
+    se = block_sum_pairwise(se, sh);
+    cnt = block_sum_pairwise(cnt, wi[0]);
+    writer = block_best(best, bidx, bz, wv[0], wi[0]);
+  } else {
+    float tv[KM];
+    int ti[KM];
+    topk_clear<KM>(tv, ti);
+    row.each([&](float xv, int c, int) { topk_insert<KM>(tv, ti, xv, c); });
+    wave_topk_rounds<KM>(tv, ti, top_k, lane, [&](int sel, float v, int i) {
+      if (lane == 0) wv[wave][sel] = v, wi[wave][sel] = i;
+    });
+    __syncthreads();
+    if (wave == 0) {  // the row's top_k of the waves' 4 top_k: lane sel keeps candidate sel
+      float cx = -INFINITY;
+      int cc = 0x7fffffff;
+      wave_merge_finalists<4>(wv, wi, top_k, lane, [&](int sel, float v, int i) {
+        if (lane == sel) cx = v, cc = i;
+      });
+      const bool in_c0 = lane < top_k;
+      const float z = in_c0 ? __fmul_rn(cx, inv_tau) : -INFINITY;
+      mx = wave_max(z);
+      const float e = in_c0 ? expf(z - mx) : 0.f;
+      bool in_c = in_c0;
+      if constexpr (NUCLEUS) {
+        // P and above(v) in one lane order, so that above(v) is P bit for bit under a column of no mass
+        float pe = 0.f, above = 0.f;
+#pragma unroll
+        for (int j = 0; j < KM; ++j) {  // lanes >= top_k hold z = -inf, e = 0
+          const float zj = __shfl(z, j, 64), ej = __shfl(e, j, 64);
+          pe += ej;
+          above += zj > z ? ej : 0.f;
+        }
+        in_c = in_c0 && above < __fmul_rn(top_p, pe);
+        cnt = __popcll(__ballot(in_c));
+      }
+      se = wave_sum(in_c ? e : 0.f);
+      best = in_c ? z + gumbel_noise(key, base + (uint32_t)cc) : -INFINITY;
+      bidx = in_c ? cc : 0x7fffffff, bz = __float_as_int(z);
+      wave_best(best, bidx, bz);
+      writer = lane == 0;
+    }
+  }
+  if (writer) {
+    write_sample(out, r, V, bidx, __int_as_float(bz), mx, se);
+    if constexpr (NUCLEUS)
+      if (count_out) count_out[r] = cnt;
+  }
+}
+
+template <bool NUCLEUS>
+static void launch_sample(const char* who, const float* logits, int R, int V, float inv_tau, int top_k, float top_p,
+                          uint64_t seed, uint32_t site, const SampleOut& out, int32_t* count_out, hipStream_t s) {
+  const std::string w(who);
+  require(R >= 1 && V >= 1 && (int64_t)R * V < ((int64_t)1 << 32), w + ": need R, V >= 1 and R * V < 2^32");
+  require(inv_tau > 0.f && inv_tau < INFINITY, w + ": temperature must be > 0 and finite");
+  require(top_k >= 0 && top_k <= 16 && top_k <= V, w + ": top_k must be in [0, min(16, num_vocab)]");
+  require(logits && out.ids && out.col >= 0 && out.logp_col >= 0, w + ": null logits / ids_out or a negative column");
+  auto go = [&](auto km) {
+    constexpr int KM = decltype(km)::value;
+    if (V <= 256 * 40) sample_kernel<40, KM, NUCLEUS><<<R, 256, 0, s>>>(logits, V, inv_tau, top_k, top_p, seed, site, out, count_out);
+    else sample_kernel<0, KM, NUCLEUS><<<R, 256, 0, s>>>(logits, V, inv_tau, top_k, top_p, seed, site, out, count_out);
+  };
+  if (top_k == 0) go(std::integral_constant<int, 0>{});
+  else with_km(top_k, go);
+  CAPGEN_HIP(hipGetLastError());
+}
+
+void sample_softmax(const float* logits, int R, int V, float inv_tau, int top_k, uint64_t seed, uint32_t site,
+                    int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids, int64_t next_ld, float* logp_out,
+                    int64_t logp_ld, int logp_col, hipStream_t s) {
+  launch_sample<false>("sample_softmax", logits, R, V, inv_tau, top_k, 1.f, seed, site,
+                       SampleOut{ids_out, ids_ld, col, next_ids, next_ld, logp_out, logp_ld, logp_col}, nullptr, s);
+}
+
+__global__ void fill_i32_kernel(int32_t* p, int n, int32_t v) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+void sample_nucleus(const float* logits, int R, int V, float inv_tau, int top_k, float top_p, uint64_t seed,
+                    uint32_t site, int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids, int64_t next_ld,
+                    float* logp_out, int64_t logp_ld, int logp_col, int32_t* count_out, hipStream_t s) {
+  require(top_p > 0.f && top_p <= 1.f, "sample_nucleus: top_p must be in (0, 1]");  // (false for a NaN)
+  if (top_p == 1.f) {  // C = C0 by definition: sample_softmax's own kernels
+    sample_softmax(logits, R, V, inv_tau, top_k, seed, site, ids_out, ids_ld, col, next_ids, next_ld, logp_out, logp_ld,
+                   logp_col, s);
+    if (count_out) {
+      fill_i32_kernel<<<(R + 255) / 256, 256, 0, s>>>(count_out, R, top_k == 0 ? V : top_k);
+      CAPGEN_HIP(hipGetLastError());
+    }
+    return;
+  }
+  launch_sample<true>("sample_nucleus", logits, R, V, inv_tau, top_k, top_p, seed, site,
+                      SampleOut{ids_out, ids_ld, col, next_ids, next_ld, logp_out, logp_ld, logp_col}, count_out, s);
+}
+
+// ---- bf16 decode selection from slab stats (GemmArgs::dec_stats) ----------------------------
+// One wave per row, 4 rows per workgroup.  The row's ceil(V/16) slab stats (8 B each, 1/8 of the
+// f32 logits) sit NS per lane in registers: one pass gives the row max M and the exp-sum
+// se = sum_c s_c exp(m_c - M) (the softmax of the selected elements is exp(x - M) / se), and each
+// lane's sorted best slabs.  Any element of the row's top k (value desc, index asc) lies in one of
+// the k best slabs under (max desc, slab asc): every slab ranked before the slab of the k-th best
+// element holds, as its maximum, a distinct element ranked before it.  So only k * 16 logits are
+// read back.  (The softmax is monotone in the logit; two logits rounding to one probability could
+// order by index differently than a full scan would -- the bf16 path is held to the fp32 engine by
+// the top-2-margin tests, the fp32 parity path keeps the exact full-row kernels above.)
+constexpr int kSlabNS = 16;  // slabs per lane: V <= 64 * 16 * 16 = 16384
+bool slab_select_ok(int V) { return V >= 1 && (V + 15) / 16 <= 64 * kSlabNS; }
+
+struct SlabRow {
+  float M, se;
+};
+// the row max and exp-sum from the stats; every lane ends with both
+__device__ __forceinline__ SlabRow slab_row_stats(const float2* __restrict__ st, int S, int lane, float (&mx)[kSlabNS]) {
+  float2 x[kSlabNS];
+  float M = -INFINITY;
+#pragma unroll
+  for (int u = 0; u < kSlabNS; ++u) {
+    const int c = lane + 64 * u;
+    x[u] = c < S ? st[c] : float2{-INFINITY, 0.f};
+    mx[u] = x[u].x;
+    M = fmaxf(M, x[u].x);
+  }
+  M = wave_max(M);
+  float se = 0.f;
+#pragma unroll
+  for (int u = 0; u < kSlabNS; ++u)
+    if (lane + 64 * u < S) se += x[u].y * __expf(x[u].x - M);
+  return SlabRow{M, wave_sum(se)};
+}
+
+__global__ void __launch_bounds__(256) slab_argmax_kernel(const float* __restrict__ logits,
+                                                          const float2* __restrict__ stats, int B, int V,
+                                                          int64_t* __restrict__ ids_out, int64_t ids_ld, int col,
+                                                          int32_t* __restrict__ next_ids, int64_t next_ld) {
+  const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;  // (whole waves)
+  const int S = (V + 15) / 16;
+  const float2* st = stats + (int64_t)b * S;
+  // best slab of this lane (max desc, slab asc), then of the wave
+  float best = -INFINITY;
+  int bidx = 0x7fffffff, bpos = lane;
+#pragma unroll
+  for (int u = 0; u < kSlabNS; ++u) {
+    const int c = lane + 64 * u;
+    if (c < S) {
+      const float m = st[c].x;
+      if (m > best) best = m, bidx = c;  // c ascends: ties keep the first
+    }
+  }
+  wave_best(best, bidx, bpos);
+  // the slab's 16 logits: the first column holding the maximum
+  const int c = bidx * 16 + lane;
+  float v = -INFINITY;
+  int vi = 0x7fffffff, vp = lane;
+  if (lane < 16 && c < V) v = logits[(int64_t)b * V + c], vi = c;
+  wave_best(v, vi, vp);
+  if (lane == 0) {
+    ids_out[(int64_t)b * ids_ld + col] = vi;
+    if (next_ids) next_ids[(int64_t)b * next_ld] = vi;
+  }
+}
+void slab_argmax(const float* logits, const float2* stats, int B, int V, int64_t* ids_out, int64_t ids_ld, int col,
+                 int32_t* next_ids, int64_t next_ld, hipStream_t s) {
+  require(slab_select_ok(V), "slab_argmax: V must be in [1, 16384]");
+  slab_argmax_kernel<<<(B + 3) / 4, 256, 0, s>>>(logits, stats, B, V, ids_out, ids_ld, col, next_ids, next_ld);
+  CAPGEN_HIP(hipGetLastError());
+}
+
+// one row's k best (value desc, index asc) from its slab stats: a wave per row, lane 0 leaves them in
+// (out_v, out_i)[0 .. k); chosen = this wave's KM-entry LDS scratch (row j = beam index)
+template <int KM>
+__device__ __forceinline__ void slab_row_topk_wave(const float* __restrict__ logits, const float2* __restrict__ stats,
+                                                   const float* __restrict__ prev, int r, int j, int V, int k,
+                                                   int logsm, int* chosen, int lane, float* out_v, int* out_i) {
+  const int S = (V + 15) / 16;
+  float mx[kSlabNS];
+  const SlabRow rs = slab_row_stats(stats + (int64_t)r * S, S, lane, mx);
+  // each lane's best KM slabs, sorted; then k wave rounds pick the row's k best slabs
+  float tv[KM];
+  int ti[KM];
+  topk_clear<KM>(tv, ti);
+#pragma unroll
+  for (int u = 0; u < kSlabNS; ++u) {
+    const int c = lane + 64 * u;
+    if (c < S) topk_insert<KM>(tv, ti, mx[u], c);
+  }
+  wave_topk_rounds<KM>(tv, ti, k, lane, [&](int sel, float, int slab) {
+    if (lane == 0) chosen[sel] = slab;  // (0x7fffffff when S < k: no such slab)
+  });
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // lane 0's LDS writes before the reads below
+  // the k * 16 candidate logits, scored exactly as the full-row kernel scores them
+  const float lse = __logf(rs.se), add = prev ? prev[r] : 0.f;
+  topk_clear<KM>(tv, ti);
+  const float* x = logits + (int64_t)r * V;
+  for (int e = lane; e < k * 16; e += 64) {
+    const int sl = chosen[e >> 4];
+    if (sl == 0x7fffffff) continue;
+    const int c = sl * 16 + (e & 15);
+    if (c >= V) continue;
+    const float xv = x[c];
+    topk_insert<KM>(tv, ti, (logsm ? (xv - rs.M) - lse : __expf(xv - rs.M) / rs.se) + add, j * V + c);
+  }
+  wave_topk_rounds<KM>(tv, ti, k, lane, [&](int sel, float v, int i) {
+    if (lane == 0) out_v[sel] = v, out_i[sel] = i;
+  });
+}
+
+template <int KM>
+__global__ void __launch_bounds__(256) slab_row_topk_kernel(const float* __restrict__ logits,
+                                                            const float2* __restrict__ stats,
+                                                            const float* __restrict__ prev, int rows, int B, int V,
+                                                            int k, int logsm, float* __restrict__ cand_v,
+                                                            int* __restrict__ cand_i) {
+  __shared__ int chosen[4][KM];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = blockIdx.x * 4 + wave;
+  if (r >= rows) return;  // (whole waves; no workgroup barrier below)
+  slab_row_topk_wave<KM>(logits, stats, prev, r, r / B, V, k, logsm, chosen[wave], lane, cand_v + (int64_t)r * k,
+                         cand_i + (int64_t)r * k);
+}
+
+// The whole beam step of one image in ONE workgroup (round 6): wave j takes beam row j * B + i's k best
+// (slab_row_topk_wave) into LDS, wave 0 merges the k_in * k finalists (beam_merge_wave, as
+// beam_merge_kernel), and every thread then moves the image's k new rows -- sequences and ids gathered
+// from their source beams with the chosen token at column t + 1, and the beam K/V row table
+// (model.py:186-198) -- which took four more launches (merge, two gathers, the row table) per token.
+template <int KM>
+__global__ void __launch_bounds__(1024) beam_slab_step_kernel(
+    const float* __restrict__ logits, const float2* __restrict__ stats, const float* __restrict__ prev, int k_in,
+    int B, int V, int k, int logsm, float* __restrict__ out_prob, int32_t* __restrict__ out_src,
+    int32_t* __restrict__ out_tok, const int64_t* __restrict__ seq_src, int64_t* __restrict__ seq_dst, int Tw,
+    const int32_t* __restrict__ ids_src, int32_t* __restrict__ ids_dst, const int32_t* __restrict__ kv_src,
+    int32_t* __restrict__ kv_dst, int Tc, int t) {
+  __shared__ int chosen[16][KM];
+  __shared__ float cv[256];
+  __shared__ int ci[256];
+  __shared__ int bsrc[16], btok[16];
+  const int i = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (wave < k_in)
+    slab_row_topk_wave<KM>(logits, stats, prev, wave * B + i, wave, V, k, logsm, chosen[wave], lane, cv + wave * k,
+                           ci + wave * k);
+  __syncthreads();
+  if (wave == 0)
+    beam_merge_wave(
+        k_in * k, k, lane, [&](int e, float& v, int& c) { v = cv[e], c = ci[e]; },
+        [&](int sel, float best, int bidx) {
+          out_prob[sel * B + i] = best;
+          out_src[sel * B + i] = bsrc[sel] = bidx / V;
+          out_tok[sel * B + i] = btok[sel] = bidx % V;
+        });
+  __syncthreads();
+  // the image's k new rows r = j * B + i from their source rows bsrc[j] * B + i (double-buffered arrays)
+  for (int e = threadIdx.x; e < k * (Tw + 2 * Tc); e += blockDim.x) {
+    const int j = e / (Tw + 2 * Tc), q = e % (Tw + 2 * Tc);
+    const int64_t r = (int64_t)j * B + i, srow = (int64_t)bsrc[j] * B + i;
+    if (q < Tw) {
+      seq_dst[r * Tw + q] = q == t + 1 ? (int64_t)btok[j] : seq_src[srow * Tw + q];
+    } else if (q < Tw + Tc) {
+      const int cc = q - Tw;
+      ids_dst[r * Tc + cc] = cc == t + 1 ? btok[j] : ids_src[srow * Tc + cc];
+    } else {
+      const int cc = q - Tw - Tc;
+      kv_dst[r * Tc + cc] = cc <= t ? kv_src[srow * Tc + cc] : (cc == t + 1 ? (int32_t)r : 0);
+    }
+  }
+}
+
+void beam_slab_step(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
+                    int logsm, float* out_prob, int32_t* out_src, int32_t* out_tok, const int64_t* seq_src,
+                    int64_t* seq_dst, int Tw, const int32_t* ids_src, int32_t* ids_dst, const int32_t* kv_src,
+                    int32_t* kv_dst, int Tc, int t, hipStream_t s) {
+  require(k >= 1 && k <= 16 && k_in >= 1 && k_in <= 16 && k_in * k <= 256, "beam_slab_step: k, k_in in [1, 16]");
+  require(slab_select_ok(V) && t + 1 < Tw && t + 1 < Tc, "beam_slab_step: V in [1, 16384], t + 1 < width");
+  if (hz::active()) {
+    using namespace hz;
+    const int R = k * B, S = (V + 15) / 16;
+    op(s, "beam_slab_step", {rd(logits, (int64_t)k_in * B * V * 4), rd(stats, (int64_t)k_in * B * S * 8),
+                             rd(prev, prev ? (int64_t)k_in * B * 4 : 0), wr(out_prob, (int64_t)k * B * 4),
+                             wr(out_src, (int64_t)k * B * 4), wr(out_tok, (int64_t)k * B * 4),
+                             rd(seq_src, (int64_t)R * Tw * 8), wr(seq_dst, (int64_t)R * Tw * 8),
+                             rd(ids_src, (int64_t)R * Tc * 4), wr(ids_dst, (int64_t)R * Tc * 4),
+                             rd(kv_src, (int64_t)R * Tc * 4), wr(kv_dst, (int64_t)R * Tc * 4)});
+  }
+  with_km(k, [&](auto km) {
+    beam_slab_step_kernel<decltype(km)::value><<<B, 64 * k_in, 0, s>>>(logits, stats, prev, k_in, B, V, k, logsm,
+                                                                       out_prob, out_src, out_tok, seq_src, seq_dst,
+                                                                       Tw, ids_src, ids_dst, kv_src, kv_dst, Tc, t);
+  });
+  CAPGEN_HIP(hipGetLastError());
+}
+
+void beam_step_topk_slab(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
+                         int logsm, float* cand_v, int32_t* cand_i, float* out_prob, int32_t* out_src,
+                         int32_t* out_tok, hipStream_t s) {
+  require(k >= 1 && k <= 16 && k_in >= 1 && k_in * k <= 256, "beam_step_topk_slab: k in [1, 16]");
+  require(slab_select_ok(V), "beam_step_topk_slab: V must be in [1, 16384]");
+  const int rows = k_in * B;
+  with_km(k, [&](auto km) {
+    slab_row_topk_kernel<decltype(km)::value><<<(rows + 3) / 4, 256, 0, s>>>(logits, stats, prev, rows, B, V, k, logsm,
+                                                                             cand_v, cand_i);
+  });
+  beam_merge_kernel<<<B, 64, 0, s>>>(cand_v, cand_i, k_in, B, V, k, out_prob, out_src, out_tok);
+  CAPGEN_HIP(hipGetLastError());
+}
+
+// ---- the generation loops' bookkeeping ------------------------------------------------------
+__global__ void init_gen_ids_kernel(int64_t* out, int rows, int width, int32_t* ids, int tcap) {
+  int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < rows * width) out[c] = (c % width) == 0 ? 1 : 0;
+  if (c < rows * tcap) ids[c] = (c % tcap) == 0 ? 1 : 0;
+}
+void init_gen_ids(int64_t* out, int rows, int width, int32_t* ids, int tcap, hipStream_t s) {
+  init_gen_ids_kernel<<<(rows * std::max(width, tcap) + 255) / 256, 256, 0, s>>>(out, rows, width, ids, tcap);
+  CAPGEN_HIP(hipGetLastError());
+}
+
+// dst row r = (j, i) <- src row (src[j][i], i); then optionally set column `col` to tok
+template <typename E>
+__global__ void beam_gather_kernel(const E* __restrict__ src, E* __restrict__ dst, int64_t row_elems,
+                                   int64_t copy_elems, const int32_t* __restrict__ bsrc, int B, int R,
+                                   const int32_t* __restrict__ tok, int col) {
+  const int r = blockIdx.y;
+  const int srow = bsrc[r] * B + (r % B);
+  const E* s = src + (int64_t)srow * row_elems;
+  E* d = dst + (int64_t)r * row_elems;
+  for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < copy_elems; c += (int64_t)gridDim.x * blockDim.x)
+    d[c] = (tok && c == col) ? (E)tok[r] : s[c];
+}
+template <typename E>
+static void beam_gather_launch(const E* src, E* dst, int row_elems, const int32_t* bsrc, int B, int R,
+                               const int32_t* tok, int col, hipStream_t s) {
+  beam_gather_kernel<E><<<dim3(1, R), 64, 0, s>>>(src, dst, row_elems, row_elems, bsrc, B, R, tok, col);
+  CAPGEN_HIP(hipGetLastError());
+}
+void beam_gather(const int64_t* src, int64_t* dst, int row_elems, const int32_t* bsrc, int B, int R,
+                 const int32_t* tok, int col, hipStream_t s) {
+  beam_gather_launch(src, dst, row_elems, bsrc, B, R, tok, col, s);
+}
+void beam_gather(const int32_t* src, int32_t* dst, int row_elems, const int32_t* bsrc, int B, int R,
+                 const int32_t* tok, int col, hipStream_t s) {
+  beam_gather_launch(src, dst, row_elems, bsrc, B, R, tok, col, s);
+}
+
+__global__ void beam_kvrow_kernel(const int32_t* __restrict__ src, int32_t* __restrict__ dst, int Tc, int t,
+                                  const int32_t* __restrict__ bsrc, int B, int R) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= R * Tc) return;
+  const int r = e / Tc, c = e % Tc;
+  const int srow = bsrc[r] * B + (r % B);
+  dst[e] = c <= t ? src[(int64_t)srow * Tc + c] : (c == t + 1 ? r : 0);
+}
+void beam_kvrow(const int32_t* src, int32_t* dst, int Tc, int t, const int32_t* bsrc, int B, int R, hipStream_t s) {
+  beam_kvrow_kernel<<<(R * Tc + 255) / 256, 256, 0, s>>>(src, dst, Tc, t, bsrc, B, R);
+  CAPGEN_HIP(hipGetLastError());
+}
+
+}  // namespace capgen

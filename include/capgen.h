@@ -178,7 +178,7 @@ int capgen_sample(capgen_t* h, const void* feats, int feats_dtype, const float* 
  * that reaches top_p, ties kept whole -- and renormalised; logp_out is the log-probability under that
  * distribution (0 where one word is left).  Same noise, counters and sites as capgen_sample: a draw is
  * the untruncated draw whenever that lies in the nucleus.  top_p in (0, 1]; top_p = 1 is capgen_sample,
- * bit for bit (the same kernels).  Everything else as capgen_sample.  Definition: csrc/ops.hip.
+ * bit for bit (the same kernels).  Everything else as capgen_sample.  Definition: csrc/select.hip.
  * Added without a change of CAPGEN_ABI_VERSION: no existing entry changed (backward compatible). */
 int capgen_sample_nucleus(capgen_t* h, const void* feats, int feats_dtype, const float* pos, int B, int N,
                           int n_samples, float temperature, int top_k, float top_p, uint64_t seed, int64_t* ids_out,
@@ -325,7 +325,7 @@ int capgen_debug_attention_bwd_wo(int B, int Lq, int Lk, int H, const void* q, c
                                   const unsigned char* key_valid, int causal, const void* dA, const void* Wo, void* dq,
                                   void* dk, void* dv, void* stream);
 
-/* Test hooks: the row-wise, loss, optimizer, selection and SCST launchers (csrc/ops.h, csrc/rl.h),
+/* Test hooks: the row-wise, loss, optimizer, selection and SCST launchers (csrc/ops.h, csrc/select.h, csrc/rl.h),
  * one launcher per call on raw device pointers and the given stream; the arguments are the
  * launcher's own (see the formula comments there), optional pointers may be NULL, dtype 0 = f32,
  * 1 = bf16.  tests/test_gpu_rowops.py compares each with a float64 restatement.
@@ -419,7 +419,7 @@ int capgen_debug_arena_checksum(const float* p, int64_t n, uint64_t* out, void* 
  * and K/V row table [.][Tc] from the source beams with the token at column t + 1. */
 int capgen_debug_argmax_softmax(const float* logits, int B, int V, int64_t* ids_out, int64_t ids_ld, int col,
                                 int32_t* next_ids, int64_t next_ld, int logsm, void* stream);
-/* The selection of capgen_sample, one row per workgroup (definition: csrc/ops.hip): token of row r by
+/* The selection of capgen_sample, one row per workgroup (definition: csrc/select.hip): token of row r by
  * Gumbel-max over z = logits[r] * inv_tau on the row's top_k logits (0: all), noise from (seed, site,
  * r * V + v) -> ids_out[r * ids_ld + col], next_ids[r * next_ld] (nullable), and its log-probability
  * -> logp_out[r * logp_ld + logp_col] (nullable). */

@@ -1,4 +1,4 @@
-"""Float64 restatement of the nucleus (top-p) selection (sample_nucleus, csrc/ops.hip), written from
+"""Float64 restatement of the nucleus (top-p) selection (sample_nucleus, csrc/select.hip), written from
 the kernel's header comment on sampling_ref's hash, noise and candidate helpers.  It never calls the
 library.
 

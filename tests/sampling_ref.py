@@ -1,4 +1,4 @@
-"""Float64 restatement of the sampled-decoding selection (sample_softmax, csrc/ops.hip), written from
+"""Float64 restatement of the sampled-decoding selection (sample_softmax, csrc/select.hip), written from
 the kernel's header comment.  It never calls the library.
 
   z_v   = logits[r][v] * inv_tau                      (an f32 product)

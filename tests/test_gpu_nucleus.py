@@ -82,7 +82,7 @@ def check(tok, lp, cnt, b, what):
 
 @pytest.mark.parametrize("R, V", CASES)
 def test_kernel_tokens_logp_and_count(R, V):
-    """sample_nucleus_kernel<40 | 0, KM 0/4/5/8/16>: exact tokens, |C_lo| <= count <= |C_hi|, logp
+    """sample_kernel<40 | 0, KM 0/4/5/8/16, NUCLEUS = true>: exact tokens, |C_lo| <= count <= |C_hi|, logp
     between the restatement's under C_hi and under C_lo (1e-5 of max |logp|), nothing else written;
     next_ids, logp_out and count_out each given and null"""
     x = case_logits(R, V)

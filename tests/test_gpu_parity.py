@@ -832,7 +832,7 @@ def test_decode_tiles_follow_graph_replayed_steps():
 
 @pytest.mark.parametrize("logsm", [False, True])
 def test_fused_beam_step_bit_identical(set_knob, logsm):
-    """The bf16 beam step's selection and reorder in one launch per image (beam_slab_step, ops.hip:
+    """The bf16 beam step's selection and reorder in one launch per image (beam_slab_step, select.hip:
     row top-k from the slab stats, the per-image merge, the sequence / id / K-V row-table gathers)
     against the separate launches (CAPGEN_FUSED_BEAM_STEP=0): C4-shape beam ids bit-identical, with
     Softmax probabilities (Transformer) and LogSoftmax (PolicyNetwork, model_RL.py:182)."""
@@ -2009,7 +2009,7 @@ def test_c4_bf16_decode_matches_fp32_within_margin():
 
 
 def test_slab_decode_selection_equals_full_row(set_knob):
-    """bf16 decode: the classifier epilogue's slab stats + k-best-slab selection (ops.hip
+    """bf16 decode: the classifier epilogue's slab stats + k-best-slab selection (select.hip
     slab_argmax / slab_row_topk_kernel) against the full-row kernels (CAPGEN_SLAB_DECODE=0) at C4
     (B=256, V=10000, beam 5).  Both read the same f32 logits (the epilogue stores v exactly as the
     plain one).  Greedy: argmax of the logits vs argmax of the softmax -- identical ids.  Beam:

@@ -1,4 +1,4 @@
-"""Every launcher of csrc/ops.h and csrc/rl.h, and the classifier GEMM's two fused epilogues, one by
+"""Every launcher of csrc/ops.h, csrc/select.h and csrc/rl.h, and the classifier GEMM's two fused epilogues, one by
 one through the capgen_debug_* hooks against a float64 restatement of the formula in the header
 comments (never the library itself), at the smallest shapes that reach every template
 instantiation and launcher branch.  Inputs come from fixed-seed CPU generators; bf16 cases hand

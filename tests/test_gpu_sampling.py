@@ -72,7 +72,7 @@ def run_kernel(x, inv_tau, top_k, seed, site, want_next=True, want_logp=True, xd
 
 @pytest.mark.parametrize("R, V", CASES)
 def test_kernel_tokens_and_logp(R, V):
-    """sample_softmax_kernel<40 | 0, KM 0/4/5/8/16>: exact tokens, logp within 1e-5 of max |logp|,
+    """sample_kernel<40 | 0, KM 0/4/5/8/16, NUCLEUS = false>: exact tokens, logp within 1e-5 of max |logp|,
     nothing else written; next_ids and logp_out each given and null"""
     x = case_logits(R, V)
     xd = torch.from_numpy(x).to(DEV)
