@@ -73,6 +73,8 @@ _SIGS = {
     "capgen_copy_logits": (C.c_int, [_P, _P, C.c_int64, _P]),
     "capgen_greedy": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P]),
     "capgen_beam": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "capgen_beam_nbest": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P, _P,
+                                    _P, _P, _P]),
     "capgen_sample": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, _P, _P,
                                 _P]),
     "capgen_sample_nucleus": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
@@ -142,6 +144,11 @@ _SIGS = {
                                               _P, _P]),
     "capgen_debug_beam_slab_step": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
                                               _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "capgen_debug_beam_step_ended": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
+                                               _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int,
+                                               _P]),
+    "capgen_debug_beam_finish": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P,
+                                           _P]),
     "capgen_debug_rl_rows": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "capgen_debug_rl_image": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "capgen_debug_rl_numer": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),

@@ -25,6 +25,24 @@ def _stream(device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def check_beam_nbest_args(beam_size, end_id, length_penalty, n_best, num_vocab):
+    """The argument rules of capgen_beam_nbest, checked before anything is allocated (the library checks
+    them again); returns (beam_size, n_best) as ints.  Each message names its argument."""
+    for name, v in (("beam_size", beam_size), ("end_id", end_id), ("n_best", n_best)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"capgen beam_nbest: {name} must be an int, not {type(v).__name__}")
+    if not 1 <= beam_size <= min(16, num_vocab):
+        raise ValueError(f"capgen beam_nbest: beam_size must be in [1, min(16, num_vocab)], not {beam_size}")
+    if not 1 <= n_best <= beam_size:
+        raise ValueError(f"capgen beam_nbest: n_best must be in [1, beam_size], not {n_best}")
+    if not -1 <= end_id < num_vocab:
+        raise ValueError(f"capgen beam_nbest: end_id must be in [-1, num_vocab), not {end_id}")
+    alpha = float(length_penalty)
+    if not (0.0 <= alpha < float("inf")):  # (false for a NaN)
+        raise ValueError(f"capgen beam_nbest: length_penalty must be finite and >= 0, not {length_penalty}")
+    return int(beam_size), int(n_best)
+
+
 class Engine:
     def __init__(self, cfg: CapgenConfig, device="cuda:0"):
         self.cfg = cfg
@@ -320,6 +338,25 @@ class Engine:
         _lib.check(self.lib.capgen_beam(self.h, _ptr(f), ft, _ptr(p), B, N, int(beam_size), _ptr(ids),
                                         _stream(self.device)))
         return ids
+
+    def beam_nbest(self, feats, pos, beam_size, end_id, length_penalty=0.0, n_best=1):
+        """The standard beam search (capgen_beam_nbest): a hypothesis stops at end_id (-1: never), finished
+        ones compete with their log-probability frozen, and the n_best of the beam_size hypotheses per image
+        come back ordered by score = logp / max(len, 1) ** length_penalty (0.0: logp itself).  Always scored
+        with the log-softmax.  Returns (ids int64 [n, B, T] laid out as beam's, zeros after <END>; score f32
+        [n, B]; logp f32 [n, B]; len int32 [n, B]: tokens through <END>, T - 1 where it never came)."""
+        beam_size, n = check_beam_nbest_args(beam_size, end_id, length_penalty, n_best, self.cfg.num_vocab)
+        f, ft, p, _ = self._inputs(feats, pos)
+        B, N, _ = f.shape
+        T = self.cfg.max_length
+        ids = torch.empty(n * B, T, dtype=torch.int64, device=self.device)
+        score = torch.empty(n * B, dtype=torch.float32, device=self.device)
+        logp = torch.empty(n * B, dtype=torch.float32, device=self.device)
+        length = torch.empty(n * B, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.capgen_beam_nbest(self.h, _ptr(f), ft, _ptr(p), B, N, beam_size, int(end_id),
+                                              float(length_penalty), n, _ptr(ids), _ptr(score), _ptr(logp),
+                                              _ptr(length), _stream(self.device)))
+        return ids.view(n, B, T), score.view(n, B), logp.view(n, B), length.view(n, B)
 
     def sample(self, feats, pos, n_samples=1, temperature=1.0, top_k=0, seed=0, want_logp=True, top_p=1.0):
         """n_samples captions per image drawn from softmax(logits / temperature) over the top_k largest

@@ -118,6 +118,14 @@ class Transformer:
     def beam_search(self, object_features, position_features, beam_size=1):
         return self.engine.beam(object_features, position_features, beam_size)
 
+    def beam_search_nbest(self, object_features, position_features, beam_size, end_id, length_penalty=0.0, n_best=1):
+        """The standard beam search (no counterpart in the reference, whose beam_search runs every hypothesis
+        to max_length and scores the tokens after <END> too): hypotheses stop at end_id, the n_best per image
+        come back ordered by logp / len ** length_penalty.  Returns (ids LongTensor [n_best, B, max_length],
+        score f32 [n_best, B], logp f32 [n_best, B], len int32 [n_best, B]) -- Engine.beam_nbest."""
+        return self.engine.beam_nbest(object_features, position_features, beam_size, end_id,
+                                      length_penalty=length_penalty, n_best=n_best)
+
     def sample_caption_vector(self, object_features, position_features, n_samples=1, temperature=1.0, top_k=0,
                               seed=None, top_p=1.0):
         """n_samples captions per image drawn from the model's distribution (temperature / top-k /

@@ -52,6 +52,19 @@ class MODEL_init:
         assert isinstance(beam_size, int)
         assert beam_size > 1 or beam_size in [None, 1]
 
+    def beam_captions(self, object_features, position_features, beam_size, length_penalty=0.0, n_best=1):
+        """The n_best captions per image of a beam search that stops at <END> (generate_caption keeps the
+        reference's search, which does not): (captions, score) -- n_best lists of B strings, best first, and
+        their scores [n_best, B] (f32, on the model's device): the caption's log-probability through <END>
+        divided by its length ** length_penalty (0.0: the log-probability itself).  A vocabulary without
+        <END> searches to max_length."""
+        end = -1 if self.end_idx is None else int(self.end_idx)
+        ids, score, _, _ = self.model.beam_search_nbest(object_features=object_features,
+                                                        position_features=position_features, beam_size=beam_size,
+                                                        end_id=end, length_penalty=length_penalty, n_best=n_best)
+        host = ids.cpu().numpy()
+        return [self.decode_captions(host[j]) for j in range(host.shape[0])], score
+
     def sample_captions(self, object_features, position_features, n_samples=1, temperature=1.0, top_k=0, seed=None,
                         top_p=1.0):
         """n_samples captions per image drawn from the model's distribution (temperature / top-k /

@@ -175,6 +175,7 @@ struct GenWS {
   int64_t *seq, *seq2;   // beam [R][Tw]
   float *bprob, *bprob2;
   int32_t *bsrc, *btok;
+  int32_t *bfin, *bfin2, *blen, *blen2;  // beam_nbest: [R] finished flag and length of each hypothesis
 };
 
 }  // namespace
@@ -1790,6 +1791,10 @@ struct capgen_engine {
     p.take(g.bprob2, R);
     p.take(g.bsrc, R);
     p.take(g.btok, R);
+    p.take(g.bfin, R);
+    p.take(g.bfin2, R);
+    p.take(g.blen, R);
+    p.take(g.blen2, R);
   }
   void ensure_gen(int R, int N) {
     if (gws && R <= g.R && N <= g.N) return;
@@ -1996,6 +2001,31 @@ struct capgen_engine {
     require(k >= 1 && k <= 16, "beam_search: beam_size must be in [1, 16]");
     require(k <= L.V, "beam_search: beam_size must be <= num_vocab");
     require(B >= 1 && N >= 1 && N <= 64, "beam_search: need B >= 1 and N in [1, 64]");
+    beam_run(feats, ft, pos, B, N, k, nullptr, s);
+    CAPGEN_HIP(hipMemcpyAsync(ids_out, g.seq, sizeof(int64_t) * B * L.maxlen, hipMemcpyDeviceToDevice, s));
+  }
+
+  // The standard beam search (definition: select.hip): a hypothesis stops at <END> (end_id; -1: never),
+  // finished hypotheses compete with their log-probability frozen, and the n_best of the k per image come
+  // back ordered by logp / len^alpha with score, logp and length.  beam's loop and launch sequence with the
+  // END-aware selection kernels (always the log-softmax); finished rows still run through the decoder and
+  // there is no early exit: nothing here waits for the device.  One more launch, beam_finish, at the end.
+  void beam_nbest(const void* feats, DType ft, const float* pos, int B, int N, int k, int end_id, float alpha,
+                  int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, hipStream_t s) {
+    require(k >= 1 && k <= 16 && k <= L.V, "beam_nbest: beam_size must be in [1, min(16, num_vocab)]");
+    require(n_best >= 1 && n_best <= k, "beam_nbest: n_best must be in [1, beam_size]");
+    require(end_id >= -1 && end_id < L.V, "beam_nbest: end_id must be in [-1, num_vocab)");
+    require(alpha >= 0.f && alpha < INFINITY, "beam_nbest: length_penalty must be finite and >= 0");  // (false for a NaN)
+    require(N >= 1 && N <= 64, "beam_nbest: N must be in [1, 64]");
+    require(B >= 1, "beam_nbest: need B >= 1");
+    require(ids_out != nullptr, "beam_nbest: null ids_out");
+    beam_run(feats, ft, pos, B, N, k, &end_id, s);
+    beam_finish(g.seq, g.bprob, g.blen, k, B, L.maxlen, alpha, n_best, ids_out, score_out, logp_out, len_out, s);
+  }
+
+  // The loop of beam (end_id == nullptr: the reference's search, model.py:135-200) and of beam_nbest: leaves
+  // the k * B hypotheses in g.seq, their scores in g.bprob and, for beam_nbest, g.bfin / g.blen.
+  void beam_run(const void* feats, DType ft, const float* pos, int B, int N, int k, const int* end_id, hipStream_t s) {
     ensure_acts(B, N, 2);
     ensure_gen(k * B, N);
     ensure_dtiles();
@@ -2009,15 +2039,38 @@ struct capgen_engine {
     // bf16: the selection and the reorder of a step as one launch per image (beam_slab_step:
     // CAPGEN_FUSED_BEAM_STEP=0 restores the top-k, merge and three reorder launches)
     const bool fused_step = slab_decode() && fused_beam_step_on && k <= 16 && Tw == Tc;
+    if (end_id) {  // every hypothesis starts live with no tokens
+      memset_async(g.bfin, sizeof(int32_t) * R, s);
+      memset_async(g.blen, sizeof(int32_t) * R, s);
+    }
+    // the END-aware step's state: read from bfin / blen, written to bfin2 / blen2, then swapped
+    auto ended = [&] { return BeamEnd{g.bfin, g.blen, g.bfin2, g.blen2, *end_id}; };
+    auto swap_ended = [&] {
+      std::swap(g.bfin, g.bfin2);
+      std::swap(g.blen, g.blen2);
+    };
     auto fused = [&](int t, const float* prev, int kin, float* out_prob) {
-      beam_slab_step(g.logits, g.dstats, prev, kin, B, L.V, k, decode_logsm, out_prob, g.bsrc, g.btok, g.seq, g.seq2,
-                     Tw, g.ids, g.ids2, g.kvrow, g.kvrow2, Tc, t, s);
+      if (end_id) {
+        beam_slab_step_ended(g.logits, g.dstats, prev, kin, B, L.V, k, out_prob, g.bsrc, g.btok, g.seq, g.seq2, Tw,
+                             g.ids, g.ids2, g.kvrow, g.kvrow2, Tc, t, ended(), s);
+        swap_ended();
+      } else {
+        beam_slab_step(g.logits, g.dstats, prev, kin, B, L.V, k, decode_logsm, out_prob, g.bsrc, g.btok, g.seq,
+                       g.seq2, Tw, g.ids, g.ids2, g.kvrow, g.kvrow2, Tc, t, s);
+      }
       std::swap(g.seq, g.seq2);
       std::swap(g.ids, g.ids2);
       std::swap(g.kvrow, g.kvrow2);
     };
+    // (beam_nbest off the fused path: the full-row kernels, which read the f32 logits of either dtype)
+    auto full_row_ended = [&](const float* prev, int kin, float* out_prob) {
+      beam_step_topk_ended(g.logits, prev, kin, B, L.V, k, g.cand_v, g.cand_i, out_prob, g.bsrc, g.btok, ended(), s);
+      swap_ended();
+    };
     if (fused_step)  // (beam 0's finalists only: every source is beam 0 at t = 0)
       fused(0, nullptr, 1, g.bprob);
+    else if (end_id)
+      full_row_ended(nullptr, 1, g.bprob);
     else if (slab_decode())
       beam_step_topk_slab(g.logits, g.dstats, nullptr, 1, B, L.V, k, decode_logsm, g.cand_v, g.cand_i, g.bprob, g.bsrc,
                           g.btok, s);
@@ -2044,7 +2097,9 @@ struct capgen_engine {
         std::swap(g.bprob, g.bprob2);
         continue;
       }
-      if (slab_decode())
+      if (end_id)
+        full_row_ended(g.bprob, k, g.bprob2);
+      else if (slab_decode())
         beam_step_topk_slab(g.logits, g.dstats, g.bprob, k, B, L.V, k, decode_logsm, g.cand_v, g.cand_i, g.bprob2,
                             g.bsrc, g.btok, s);
       else
@@ -2053,7 +2108,6 @@ struct capgen_engine {
       std::swap(g.bprob, g.bprob2);
       reorder(t);
     }
-    CAPGEN_HIP(hipMemcpyAsync(ids_out, g.seq, sizeof(int64_t) * B * Tw, hipMemcpyDeviceToDevice, s));
   }
 
   // Sampled decoding: n draws per image from softmax(logits / temperature) over the top_k logits
@@ -2505,6 +2559,19 @@ int capgen_beam(capgen_t* h, const void* feats, int ft, const float* pos, int B,
     hipStream_t cs = (hipStream_t)stream;
     h->enter(cs);
     h->beam(feats, dt(ft), pos, B, N, k, ids_out, h->es);
+    h->leave(cs);
+  });
+}
+
+int capgen_beam_nbest(capgen_t* h, const void* feats, int ft, const float* pos, int B, int N, int k, int end_id,
+                      float length_penalty, int n_best, int64_t* ids_out, float* score_out, float* logp_out,
+                      int32_t* len_out, void* stream) {
+  return guarded([&] {
+    set_device(h);
+    hipStream_t cs = (hipStream_t)stream;
+    h->enter(cs);
+    h->beam_nbest(feats, dt(ft), pos, B, N, k, end_id, length_penalty, n_best, ids_out, score_out, logp_out, len_out,
+                  h->es);
     h->leave(cs);
   });
 }
@@ -3000,6 +3067,34 @@ int capgen_debug_beam_slab_step(const float* logits, const void* stats, const fl
     require(t >= 0, "debug_beam_slab_step: t >= 0");
     beam_slab_step(logits, reinterpret_cast<const float2*>(stats), prev, k_in, B, V, k, logsm, out_prob, out_src,
                    out_tok, seq_src, seq_dst, Tw, ids_src, ids_dst, kv_src, kv_dst, Tc, t, (hipStream_t)stream);
+  });
+}
+
+int capgen_debug_beam_step_ended(const float* logits, const void* stats, const float* prev, int k_in, int B, int V,
+                                 int k, int end_id, const int32_t* fin_src, const int32_t* len_src, int32_t* fin_dst,
+                                 int32_t* len_dst, float* cand_v, int32_t* cand_i, float* out_prob, int32_t* out_src,
+                                 int32_t* out_tok, const int64_t* seq_src, int64_t* seq_dst, int Tw,
+                                 const int32_t* ids_src, int32_t* ids_dst, const int32_t* kv_src, int32_t* kv_dst,
+                                 int Tc, int t, void* stream) {
+  return guarded([&] {
+    const hipStream_t s = (hipStream_t)stream;
+    const BeamEnd e{fin_src, len_src, fin_dst, len_dst, end_id};
+    if (stats) {
+      require(t >= 0, "debug_beam_step_ended: t >= 0");
+      beam_slab_step_ended(logits, reinterpret_cast<const float2*>(stats), prev, k_in, B, V, k, out_prob, out_src,
+                           out_tok, seq_src, seq_dst, Tw, ids_src, ids_dst, kv_src, kv_dst, Tc, t, e, s);
+    } else {
+      beam_step_topk_ended(logits, prev, k_in, B, V, k, cand_v, cand_i, out_prob, out_src, out_tok, e, s);
+    }
+  });
+}
+
+int capgen_debug_beam_finish(const int64_t* seq, const float* logp, const int32_t* len, int k, int B, int Tw,
+                             float length_penalty, int n_best, int64_t* ids_out, float* score_out, float* logp_out,
+                             int32_t* len_out, void* stream) {
+  return guarded([&] {
+    beam_finish(seq, logp, len, k, B, Tw, length_penalty, n_best, ids_out, score_out, logp_out, len_out,
+                (hipStream_t)stream);
   });
 }
 

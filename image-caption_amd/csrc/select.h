@@ -45,6 +45,30 @@ void beam_step_topk_slab(const float* logits, const float2* stats, const float* 
                          int logsm, float* cand_v, int32_t* cand_i, float* out_prob, int32_t* out_src,
                          int32_t* out_tok, hipStream_t s);
 
+// The END-aware beam step (beam_nbest; definition: select.hip): a finished source row offers one candidate
+// (its logp, token 0) whatever its logits hold, a live one its log-softmax scores (always, as logsm = 1
+// scores them).  fin / len of the k_in * B source rows are read, those of the k * B new rows written.
+struct BeamEnd {
+  const int32_t* fin_src;
+  const int32_t* len_src;
+  int32_t* fin_dst;
+  int32_t* len_dst;
+  int end_id;  // -1: nothing ever finishes
+};
+// full-row kernels + merge (as beam_step_topk) and the one-launch slab step (as beam_slab_step)
+void beam_step_topk_ended(const float* logits, const float* prev, int k_in, int B, int V, int k, float* cand_v,
+                          int32_t* cand_i, float* out_prob, int32_t* out_src, int32_t* out_tok, const BeamEnd& e,
+                          hipStream_t s);
+void beam_slab_step_ended(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
+                          float* out_prob, int32_t* out_src, int32_t* out_tok, const int64_t* seq_src,
+                          int64_t* seq_dst, int Tw, const int32_t* ids_src, int32_t* ids_dst, const int32_t* kv_src,
+                          int32_t* kv_dst, int Tc, int t, const BeamEnd& e, hipStream_t s);
+// the end of the search: score = logp (alpha == 0) or logp / max(len, 1)^alpha; per image the n_best of the
+// k hypotheses (rows j * B + i of seq [k * B][Tw], logp, len) under (score desc, beam asc) -> row
+// rank * B + i of ids_out [n_best * B][Tw], score_out, logp_out, len_out (the last three nullable)
+void beam_finish(const int64_t* seq, const float* logp, const int32_t* len, int k, int B, int Tw, float alpha,
+                 int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, hipStream_t s);
+
 // the generation loops' bookkeeping
 // out [rows][width] (int64) and ids [rows][tcap] (int32): column 0 = <START> (1), the rest 0
 void init_gen_ids(int64_t* out, int rows, int width, int32_t* ids, int tcap, hipStream_t s);

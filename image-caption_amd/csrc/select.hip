@@ -77,18 +77,73 @@ void argmax_softmax(const float* logits, int B, int V, int64_t* ids_out, int64_t
 // top-KM, and the row's top k.  Part 2, one wave per image: top k of its k_in rows' k
 // finalists each -- every image-level winner is in its row's top k.  Neither the [R, V]
 // probabilities nor a [B, k*V] scan exist: one read of the logits per step.
+//
+// ---- the END-aware beam step (beam_nbest; the ENDED = true forms of the kernels below) and its finish ----
+// T = max_length, V = num_vocab, k = beam_size; rows are j * B + i, beam j of image i.  A hypothesis is
+// its tokens, logp (the f32 running sum of its token log-probabilities), len (int32: the tokens emitted
+// while live, <END> included) and the flag fin.  It starts as <START> with logp = 0, len = 0, fin = 0;
+// at step 0 only beam 0 is a source.
+// - Candidates of image i at a step.  A live source row j offers (logp_j + logsoftmax(logits[j*B+i])[v],
+//   flat index j * V + v) for every v: always the log-softmax, scored by the logsm = 1 arithmetic of the
+//   reference step in the same order, so with nothing finished the results are bit-identical to it.  A
+//   finished source row j offers exactly one candidate, (logp_j, j * V + 0); its logits and slab stats are
+//   never read (they may be NaN).  The k best are taken under (score descending, flat index ascending) --
+//   two finished rows with bit-equal logp keep their beam order.  Pruning uses the raw logp.
+// - Update for the selected (j, v).  From a finished source: token 0 is appended and logp, len, fin are
+//   copied.  From a live source: token v is appended, len + 1, fin = (v == end_id); end_id = -1: nothing
+//   ever finishes.
+// - Fewer than k candidates (only where a caller hands in fewer than k live sources' worth: the engine
+//   never does): the slots left over get score -inf, source 0, token 0 and source 0's state copied.
+// - Finish (beam_finish_kernel).  Final score s = logp when alpha == 0 (by definition: the launcher picks
+//   the form that does not divide), else s = logp / powf((float)max(len, 1), alpha).  Per image the
+//   hypotheses are ordered by (s descending, beam index ascending; a NaN s ranks as -inf) and the first
+//   n_best are written: tokens, s, logp and len.  A hypothesis that never finished has len = T - 1.
+
+// lane 0 of a merge, slot sel of image i: the selected (score, flat index) -> outputs and the new state
+__device__ __forceinline__ void beam_end_emit(const BeamEnd& e, int sel, int i, int B, int V, float best, int bidx,
+                                              float* out_prob, int32_t* out_src, int32_t* out_tok, int& src,
+                                              int& tok) {
+  const bool none = bidx == 0x7fffffff;  // fewer than k candidates
+  src = none ? 0 : bidx / V, tok = none ? 0 : bidx % V;
+  const int srow = src * B + i, f = e.fin_src[srow], l = e.len_src[srow];
+  out_prob[sel * B + i] = best;
+  out_src[sel * B + i] = src;
+  out_tok[sel * B + i] = tok;
+  e.fin_dst[sel * B + i] = (f || none) ? f : (tok == e.end_id);
+  e.len_dst[sel * B + i] = (f || none) ? l : l + 1;
+}
+// a finished source row's k finalists: (logp, j * V) and k - 1 empty slots; threads 0 .. k - 1 of its wave
+__device__ __forceinline__ void beam_end_finalists(const float* prev, int r, int j, int V, int k, int lane,
+                                                   float* out_v, int* out_i) {
+  if (lane < k) {
+    out_v[lane] = lane == 0 ? (prev ? prev[r] : 0.f) : -INFINITY;
+    out_i[lane] = lane == 0 ? j * V : 0x7fffffff;
+  }
+}
+
+// the last argument of a step kernel: the END-aware form's state, nothing in the reference form
+struct NoBeamEnd {};
+template <bool ENDED>
+using BeamEndArg = std::conditional_t<ENDED, BeamEnd, NoBeamEnd>;
 
 // NT threads per row (W = NT / 64 waves), NV values per thread in registers (V <= NT * NV)
-template <int KM, int NV, int NT = 256>
+// ENDED: e.fin_src [rows] marks the finished source rows (see above) and logsm is 1; false: the reference step
+template <int KM, int NV, int NT = 256, bool ENDED = false>
 __global__ void __launch_bounds__(NT) beam_row_topk_kernel(const float* __restrict__ logits,
                                                             const float* __restrict__ prev, int B, int V, int k,
                                                             int logsm, float* __restrict__ cand_v,
-                                                            int* __restrict__ cand_i) {
+                                                            int* __restrict__ cand_i, BeamEndArg<ENDED> e) {
   constexpr int W = NT / 64;
   __shared__ float sh[W];
   __shared__ float wv[W][16];
   __shared__ int wi[W][16];
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = r / B;
+  if constexpr (ENDED) {
+    if (e.fin_src[r]) {  // (the whole workgroup: no barrier is skipped by some threads only)
+      if (wave == 0) beam_end_finalists(prev, r, j, V, k, lane, cand_v + (int64_t)r * k, cand_i + (int64_t)r * k);
+      return;
+    }
+  }
   RowRegs<NV, NT> row(logits + (int64_t)r * V, V, tid);
   float mx = -INFINITY;
   row.each([&](float xv, int, int) { mx = fmaxf(mx, xv); });
@@ -161,16 +216,35 @@ __global__ void __launch_bounds__(64) beam_merge_kernel(const float* __restrict_
         out_tok[sel * B + i] = bidx % V;
       });
 }
+// the END-aware merge: the same selection, then the new rows' fin / len from their sources'
+__global__ void __launch_bounds__(64) beam_merge_ended_kernel(const float* __restrict__ cand_v,
+                                                              const int* __restrict__ cand_i, int k_in, int B, int V,
+                                                              int k, float* __restrict__ out_prob,
+                                                              int32_t* __restrict__ out_src,
+                                                              int32_t* __restrict__ out_tok, BeamEnd e) {
+  const int i = blockIdx.x;
+  beam_merge_wave(
+      k_in * k, k, threadIdx.x,
+      [&](int en, float& v, int& c) {
+        const int64_t src = ((int64_t)(en / k) * B + i) * k + en % k;
+        v = cand_v[src], c = cand_i[src];
+      },
+      [&](int sel, float best, int bidx) {
+        int src, tok;
+        beam_end_emit(e, sel, i, B, V, best, bidx, out_prob, out_src, out_tok, src, tok);
+      });
+}
 
-template <int KM>
+template <int KM, bool ENDED = false>
 static void beam_row_topk(const float* logits, const float* prev, int rows, int B, int V, int k, int logsm,
-                          float* cand_v, int32_t* cand_i, hipStream_t s) {
+                          float* cand_v, int32_t* cand_i, hipStream_t s, BeamEndArg<ENDED> e = {}) {
   // 512 threads per row where the row fits 20 values per thread (42 vs 50 us per token at B = 1280
   // with 256 threads, round 2)
   if (V <= 512 * 20 && KM * 8 <= 64)
-    beam_row_topk_kernel<KM, 20, 512><<<rows, 512, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i);
-  else if (V <= 256 * 40) beam_row_topk_kernel<KM, 40><<<rows, 256, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i);
-  else beam_row_topk_kernel<KM, 0><<<rows, 256, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i);
+    beam_row_topk_kernel<KM, 20, 512, ENDED><<<rows, 512, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i, e);
+  else if (V <= 256 * 40)
+    beam_row_topk_kernel<KM, 40, 256, ENDED><<<rows, 256, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i, e);
+  else beam_row_topk_kernel<KM, 0, 256, ENDED><<<rows, 256, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i, e);
 }
 
 void beam_step_topk(const float* logits, const float* prev, int k_in, int B, int V, int k, int logsm, float* cand_v,
@@ -180,6 +254,35 @@ void beam_step_topk(const float* logits, const float* prev, int k_in, int B, int
     beam_row_topk<decltype(km)::value>(logits, prev, k_in * B, B, V, k, logsm, cand_v, cand_i, s);
   });
   beam_merge_kernel<<<B, 64, 0, s>>>(cand_v, cand_i, k_in, B, V, k, out_prob, out_src, out_tok);
+  CAPGEN_HIP(hipGetLastError());
+}
+
+static void require_beam_end(const char* who, int V, const BeamEnd& e) {
+  const std::string w(who);
+  require(e.fin_src && e.len_src && e.fin_dst && e.len_dst, w + ": null fin / len");
+  require(e.fin_src != e.fin_dst && e.len_src != e.len_dst, w + ": fin / len must be double-buffered");
+  require(e.end_id >= -1 && e.end_id < V, w + ": end_id must be in [-1, num_vocab)");
+}
+
+void beam_step_topk_ended(const float* logits, const float* prev, int k_in, int B, int V, int k, float* cand_v,
+                          int32_t* cand_i, float* out_prob, int32_t* out_src, int32_t* out_tok, const BeamEnd& e,
+                          hipStream_t s) {
+  require(k >= 1 && k <= 16 && k_in >= 1 && k_in * k <= 256, "beam_step_topk_ended: k in [1, 16]");
+  require_beam_end("beam_step_topk_ended", V, e);
+  if (hz::active()) {
+    using namespace hz;
+    const int64_t Rin = (int64_t)k_in * B, R = (int64_t)k * B;
+    op(s, "beam_row_topk_ended", {rd(logits, Rin * V * 4), rd(prev, prev ? Rin * 4 : 0), rd(e.fin_src, Rin * 4),
+                                  wr(cand_v, Rin * k * 4), wr(cand_i, Rin * k * 4)});
+    op(s, "beam_merge_ended", {rd(cand_v, Rin * k * 4), rd(cand_i, Rin * k * 4), rd(e.fin_src, Rin * 4),
+                               rd(e.len_src, Rin * 4), wr(out_prob, R * 4), wr(out_src, R * 4), wr(out_tok, R * 4),
+                               wr(e.fin_dst, R * 4), wr(e.len_dst, R * 4)});
+  }
+  with_km(k, [&](auto km) {
+    beam_row_topk<decltype(km)::value, true>(logits, prev, k_in * B, B, V, k, 1, cand_v, cand_i, s, e);
+  });
+  beam_merge_ended_kernel<<<B, 64, 0, s>>>(cand_v, cand_i, k_in, B, V, k, out_prob, out_src, out_tok,
+                                           e);
   CAPGEN_HIP(hipGetLastError());
 }
 
@@ -517,10 +620,15 @@ void slab_argmax(const float* logits, const float2* stats, int B, int V, int64_t
 
 // one row's k best (value desc, index asc) from its slab stats: a wave per row, lane 0 leaves them in
 // (out_v, out_i)[0 .. k); chosen = this wave's KM-entry LDS scratch (row j = beam index)
-template <int KM>
+// ENDED: a finished row (done, the END-aware step above) offers its one candidate and reads nothing else
+template <int KM, bool ENDED = false>
 __device__ __forceinline__ void slab_row_topk_wave(const float* __restrict__ logits, const float2* __restrict__ stats,
                                                    const float* __restrict__ prev, int r, int j, int V, int k,
-                                                   int logsm, int* chosen, int lane, float* out_v, int* out_i) {
+                                                   int logsm, int* chosen, int lane, float* out_v, int* out_i,
+                                                   bool done = false) {
+  if constexpr (ENDED) {
+    if (done) return beam_end_finalists(prev, r, j, V, k, lane, out_v, out_i);  // (the whole wave)
+  }
   const int S = (V + 15) / 16;
   float mx[kSlabNS];
   const SlabRow rs = slab_row_stats(stats + (int64_t)r * S, S, lane, mx);
@@ -573,29 +681,38 @@ __global__ void __launch_bounds__(256) slab_row_topk_kernel(const float* __restr
 // beam_merge_kernel), and every thread then moves the image's k new rows -- sequences and ids gathered
 // from their source beams with the chosen token at column t + 1, and the beam K/V row table
 // (model.py:186-198) -- which took four more launches (merge, two gathers, the row table) per token.
-template <int KM>
+// ENDED: the END-aware step (above): finished rows offer one candidate, lane 0 of the merge also writes the
+// new rows' fin / len (e: double-buffered like the other arrays) and logsm is 1; false: the reference step
+template <int KM, bool ENDED = false>
 __global__ void __launch_bounds__(1024) beam_slab_step_kernel(
     const float* __restrict__ logits, const float2* __restrict__ stats, const float* __restrict__ prev, int k_in,
     int B, int V, int k, int logsm, float* __restrict__ out_prob, int32_t* __restrict__ out_src,
     int32_t* __restrict__ out_tok, const int64_t* __restrict__ seq_src, int64_t* __restrict__ seq_dst, int Tw,
     const int32_t* __restrict__ ids_src, int32_t* __restrict__ ids_dst, const int32_t* __restrict__ kv_src,
-    int32_t* __restrict__ kv_dst, int Tc, int t) {
+    int32_t* __restrict__ kv_dst, int Tc, int t, BeamEndArg<ENDED> e) {
   __shared__ int chosen[16][KM];
   __shared__ float cv[256];
   __shared__ int ci[256];
   __shared__ int bsrc[16], btok[16];
   const int i = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (wave < k_in)
-    slab_row_topk_wave<KM>(logits, stats, prev, wave * B + i, wave, V, k, logsm, chosen[wave], lane, cv + wave * k,
-                           ci + wave * k);
+  if (wave < k_in) {
+    bool done = false;
+    if constexpr (ENDED) done = e.fin_src[wave * B + i] != 0;
+    slab_row_topk_wave<KM, ENDED>(logits, stats, prev, wave * B + i, wave, V, k, logsm, chosen[wave], lane,
+                                  cv + wave * k, ci + wave * k, done);
+  }
   __syncthreads();
   if (wave == 0)
     beam_merge_wave(
-        k_in * k, k, lane, [&](int e, float& v, int& c) { v = cv[e], c = ci[e]; },
+        k_in * k, k, lane, [&](int en, float& v, int& c) { v = cv[en], c = ci[en]; },
         [&](int sel, float best, int bidx) {
-          out_prob[sel * B + i] = best;
-          out_src[sel * B + i] = bsrc[sel] = bidx / V;
-          out_tok[sel * B + i] = btok[sel] = bidx % V;
+          if constexpr (ENDED) {
+            beam_end_emit(e, sel, i, B, V, best, bidx, out_prob, out_src, out_tok, bsrc[sel], btok[sel]);
+          } else {
+            out_prob[sel * B + i] = best;
+            out_src[sel * B + i] = bsrc[sel] = bidx / V;
+            out_tok[sel * B + i] = btok[sel] = bidx % V;
+          }
         });
   __syncthreads();
   // the image's k new rows r = j * B + i from their source rows bsrc[j] * B + i (double-buffered arrays)
@@ -633,8 +750,88 @@ void beam_slab_step(const float* logits, const float2* stats, const float* prev,
   with_km(k, [&](auto km) {
     beam_slab_step_kernel<decltype(km)::value><<<B, 64 * k_in, 0, s>>>(logits, stats, prev, k_in, B, V, k, logsm,
                                                                        out_prob, out_src, out_tok, seq_src, seq_dst,
-                                                                       Tw, ids_src, ids_dst, kv_src, kv_dst, Tc, t);
+                                                                       Tw, ids_src, ids_dst, kv_src, kv_dst, Tc, t,
+                                                                       NoBeamEnd{});
   });
+  CAPGEN_HIP(hipGetLastError());
+}
+
+void beam_slab_step_ended(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
+                          float* out_prob, int32_t* out_src, int32_t* out_tok, const int64_t* seq_src,
+                          int64_t* seq_dst, int Tw, const int32_t* ids_src, int32_t* ids_dst, const int32_t* kv_src,
+                          int32_t* kv_dst, int Tc, int t, const BeamEnd& e, hipStream_t s) {
+  require(k >= 1 && k <= 16 && k_in >= 1 && k_in <= 16 && k_in * k <= 256, "beam_slab_step_ended: k, k_in in [1, 16]");
+  require(slab_select_ok(V) && t + 1 < Tw && t + 1 < Tc, "beam_slab_step_ended: V in [1, 16384], t + 1 < width");
+  require_beam_end("beam_slab_step_ended", V, e);
+  if (hz::active()) {
+    using namespace hz;
+    const int64_t R = (int64_t)k * B, Rin = (int64_t)k_in * B, S = (V + 15) / 16;
+    op(s, "beam_slab_step_ended", {rd(logits, Rin * V * 4), rd(stats, Rin * S * 8), rd(prev, prev ? Rin * 4 : 0),
+                                   rd(e.fin_src, Rin * 4), rd(e.len_src, Rin * 4), wr(e.fin_dst, R * 4),
+                                   wr(e.len_dst, R * 4), wr(out_prob, R * 4), wr(out_src, R * 4), wr(out_tok, R * 4),
+                                   rd(seq_src, R * Tw * 8), wr(seq_dst, R * Tw * 8), rd(ids_src, R * Tc * 4),
+                                   wr(ids_dst, R * Tc * 4), rd(kv_src, R * Tc * 4), wr(kv_dst, R * Tc * 4)});
+  }
+  with_km(k, [&](auto km) {
+    beam_slab_step_kernel<decltype(km)::value, true><<<B, 64 * k_in, 0, s>>>(logits, stats, prev, k_in, B, V, k, 1,
+                                                                             out_prob, out_src, out_tok, seq_src,
+                                                                             seq_dst, Tw, ids_src, ids_dst, kv_src,
+                                                                             kv_dst, Tc, t, e);
+  });
+  CAPGEN_HIP(hipGetLastError());
+}
+
+// The end of the END-aware search (definition above), one wave per image, lane j = hypothesis j (k <= 16):
+// the final scores, each hypothesis' rank by counting the ones ordered before it, then the n_best rows.
+// NORM = false: alpha == 0, the score is logp itself.
+template <bool NORM>
+__global__ void __launch_bounds__(64) beam_finish_kernel(const int64_t* __restrict__ seq, const float* __restrict__ logp,
+                                                         const int32_t* __restrict__ len, int k, int B, int Tw,
+                                                         float alpha, int n_best, int64_t* __restrict__ ids_out,
+                                                         float* __restrict__ score_out, float* __restrict__ logp_out,
+                                                         int32_t* __restrict__ len_out) {
+  __shared__ int order[16];  // order[rank] = hypothesis
+  const int i = blockIdx.x, lane = threadIdx.x;
+  const bool on = lane < k;
+  const float lp = on ? logp[lane * B + i] : 0.f;
+  const int ln = on ? len[lane * B + i] : 0;
+  float sc = lp;
+  if constexpr (NORM) sc = lp / powf((float)max(ln, 1), alpha);
+  const float key = sc == sc ? sc : -INFINITY;  // (a NaN ranks last among equals, by beam index)
+  int rank = 0;
+  for (int j = 0; j < k; ++j) {
+    const float kj = __shfl(key, j, 64);
+    rank += (kj > key || (kj == key && j < lane)) ? 1 : 0;
+  }
+  if (on && rank < n_best) {
+    order[rank] = lane;
+    if (score_out) score_out[rank * B + i] = sc;
+    if (logp_out) logp_out[rank * B + i] = lp;
+    if (len_out) len_out[rank * B + i] = ln;
+  }
+  __syncthreads();
+  for (int en = lane; en < n_best * Tw; en += 64) {
+    const int rk = en / Tw, q = en % Tw;
+    ids_out[((int64_t)rk * B + i) * Tw + q] = seq[((int64_t)order[rk] * B + i) * Tw + q];
+  }
+}
+void beam_finish(const int64_t* seq, const float* logp, const int32_t* len, int k, int B, int Tw, float alpha,
+                 int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, hipStream_t s) {
+  require(k >= 1 && k <= 16, "beam_finish: beam_size must be in [1, 16]");
+  require(n_best >= 1 && n_best <= k, "beam_finish: n_best must be in [1, beam_size]");
+  require(alpha >= 0.f && alpha < INFINITY, "beam_finish: length_penalty must be finite and >= 0");  // (false for a NaN)
+  require(B >= 1 && Tw >= 1 && seq && logp && len && ids_out, "beam_finish: need B, width >= 1 and non-null arrays");
+  if (hz::active()) {
+    using namespace hz;
+    const int64_t R = (int64_t)k * B, Ro = (int64_t)n_best * B;
+    op(s, "beam_finish", {rd(seq, R * Tw * 8), rd(logp, R * 4), rd(len, R * 4), wr(ids_out, Ro * Tw * 8),
+                          wr(score_out, score_out ? Ro * 4 : 0), wr(logp_out, logp_out ? Ro * 4 : 0),
+                          wr(len_out, len_out ? Ro * 4 : 0)});
+  }
+  if (alpha == 0.f)
+    beam_finish_kernel<false><<<B, 64, 0, s>>>(seq, logp, len, k, B, Tw, alpha, n_best, ids_out, score_out, logp_out, len_out);
+  else
+    beam_finish_kernel<true><<<B, 64, 0, s>>>(seq, logp, len, k, B, Tw, alpha, n_best, ids_out, score_out, logp_out, len_out);
   CAPGEN_HIP(hipGetLastError());
 }
 

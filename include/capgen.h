@@ -160,6 +160,26 @@ int capgen_greedy(capgen_t* h, const void* feats, int feats_dtype, const float* 
 int capgen_beam(capgen_t* h, const void* feats, int feats_dtype, const float* pos, int B, int N, int beam_size,
                 int64_t* ids_out, void* stream);
 
+/* The standard beam search: capgen_beam's loop (one encoder pass, KV-cached, the same launch sequence) with
+ * <END> honoured.  A hypothesis is live until it emits end_id (-1: nothing ever finishes); a live hypothesis
+ * offers logp + log-softmax of its logits for every word (always the log-softmax, whatever
+ * capgen_set_decode_log_softmax says), a finished one offers itself once with its logp frozen and gets
+ * token 0 appended; the beam_size best survive under (logp descending, flat index ascending).  At the end
+ * score = logp when length_penalty == 0, else logp / max(len, 1)^length_penalty, with len the tokens
+ * emitted while live (<END> included; max_length - 1 for a hypothesis that never finished), and the n_best
+ * per image under (score descending, beam ascending) come back.  Pruning during the search uses the raw
+ * logp; finished rows still run through the decoder; there is no early exit.  Definition: csrc/select.hip.
+ * beam_size in [1, min(16, num_vocab)], n_best in [1, beam_size], end_id in [-1, num_vocab),
+ * length_penalty finite and >= 0, N in [1, 64].  All outputs on the device.
+ * Added without a change of CAPGEN_ABI_VERSION: no existing entry changed (backward compatible). */
+int capgen_beam_nbest(capgen_t* h, const void* feats, int feats_dtype, const float* pos, int B, int N,
+                      int beam_size, int end_id, float length_penalty, int n_best,
+                      int64_t* ids_out,   /* [n_best*B, max_length], row j*B+b = j-th best of image b, col 0 = <START> */
+                      float* score_out,   /* [n_best*B] final score, nullable */
+                      float* logp_out,    /* [n_best*B] raw log-probability, nullable */
+                      int32_t* len_out,   /* [n_best*B], nullable */
+                      void* stream);
+
 /* Sampled decoding: n_samples captions per image drawn from the model's distribution, one encoder
  * pass, KV-cached.  Position t draws token ~ softmax(logits / temperature) restricted to the top_k
  * largest logits (top_k = 0: the whole vocabulary) by Gumbel-max over the counter hash of (seed,
@@ -442,6 +462,21 @@ int capgen_debug_beam_slab_step(const float* logits, const void* stats, const fl
                                 int k, int logsm, float* out_prob, int32_t* out_src, int32_t* out_tok,
                                 const int64_t* seq_src, int64_t* seq_dst, int Tw, const int32_t* ids_src,
                                 int32_t* ids_dst, const int32_t* kv_src, int32_t* kv_dst, int Tc, int t, void* stream);
+/* One step of capgen_beam_nbest's selection (definition: csrc/select.hip).  stats == NULL: the full-row
+ * kernels plus merge (cand_v / cand_i as capgen_debug_beam_step_topk; seq / ids / kv and t unused); else the
+ * one-launch slab step (as capgen_debug_beam_slab_step; cand_v / cand_i unused).  fin_src / len_src
+ * [k_in * B] in, fin_dst / len_dst [k * B] out.  The step needs at least k candidates per image. */
+int capgen_debug_beam_step_ended(const float* logits, const void* stats, const float* prev, int k_in, int B, int V,
+                                 int k, int end_id, const int32_t* fin_src, const int32_t* len_src, int32_t* fin_dst,
+                                 int32_t* len_dst, float* cand_v, int32_t* cand_i, float* out_prob, int32_t* out_src,
+                                 int32_t* out_tok, const int64_t* seq_src, int64_t* seq_dst, int Tw,
+                                 const int32_t* ids_src, int32_t* ids_dst, const int32_t* kv_src, int32_t* kv_dst,
+                                 int Tc, int t, void* stream);
+/* The end of capgen_beam_nbest: the n_best of the k hypotheses (rows j * B + i of seq [k * B][Tw], logp, len)
+ * per image by logp / max(len, 1)^length_penalty -> ids_out [n_best * B][Tw], score / logp / len (nullable). */
+int capgen_debug_beam_finish(const int64_t* seq, const float* logp, const int32_t* len, int k, int B, int Tw,
+                             float length_penalty, int n_best, int64_t* ids_out, float* score_out, float* logp_out,
+                             int32_t* len_out, void* stream);
 /* SCST kernels (csrc/rl.hip): rows = sample (argmax log-softmax), lse, logp[sample], entropy per logit
  * row; image = per-image masked mean entropy, scal[0] = sum(mask); numer: scal[1] = -sum logp mask
  * score; loss: out = {(1-w) lm + w struct, lm, struct}; grad = the fully scaled d loss / d logits. */

@@ -5,6 +5,9 @@ sample1 / sample5: sampled decoding (Engine.sample, n_samples 1 / 5, top_k 0, te
 decode steps of greedy (B rows) / beam-5 (5 B rows) with one selection launch per token, so they are
 read against those two modes of the same run.  sample1p / sample5p: the same with top_p = 0.9 (nucleus
 sampling).  The random-init weights give nearly flat logits, the worst case of the nucleus selection.
+beam5e / beam5en: the beam search that stops at <END> (Engine.beam_nbest, beam 5, <END> = id 2) with
+length_penalty 0 and n_best 1 / length_penalty 1 and n_best 5 -- beam5's launches plus one finish kernel, read
+against beam5 of the same run.
 
 Algorithmic work (KV-cached count): beam-5 1776.7 GFLOP, greedy 699.4 GFLOP per
 256-image batch.  The reference CPU path (no KV cache) took 25.0 s (beam) / 5.87 s (greedy) per
@@ -25,7 +28,7 @@ from capgen.params import reference_init_state_dict  # noqa: E402
 from capgen.synthetic import synthetic_batch  # noqa: E402
 
 GFLOP = {"beam5": 1776.7, "greedy": 699.4, "sample1": 699.4, "sample5": 1776.7,  # (sampleN: its decode steps')
-         "sample1p": 699.4, "sample5p": 1776.7}
+         "sample1p": 699.4, "sample5p": 1776.7, "beam5e": 1776.7, "beam5en": 1776.7}
 
 
 def main():
@@ -33,7 +36,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1, help="untimed calls first (the first one tunes GEMM shapes and sizes the workspaces)")
-    ap.add_argument("--modes", default="beam5,greedy", help="of beam5, greedy, sample1, sample5, sample1p, sample5p")
+    ap.add_argument("--modes", default="beam5,greedy", help="of beam5, greedy, sample1, sample5, sample1p, sample5p, beam5e, beam5en")
     args = ap.parse_args()
     cfg = preset("C2", dtype="bf16")
     dev = torch.device("cuda", 0)
@@ -48,7 +51,9 @@ def main():
     runs = {"beam5": lambda: eng.beam(f, p, 5), "greedy": lambda: eng.greedy(f, p, want_attention=False),
             "sample1": lambda: eng.sample(f, p, n_samples=1, seed=1), "sample5": lambda: eng.sample(f, p, n_samples=5, seed=1),
             "sample1p": lambda: eng.sample(f, p, n_samples=1, seed=1, top_p=0.9),
-            "sample5p": lambda: eng.sample(f, p, n_samples=5, seed=1, top_p=0.9)}
+            "sample5p": lambda: eng.sample(f, p, n_samples=5, seed=1, top_p=0.9),
+            "beam5e": lambda: eng.beam_nbest(f, p, 5, 2, length_penalty=0.0, n_best=1),
+            "beam5en": lambda: eng.beam_nbest(f, p, 5, 2, length_penalty=1.0, n_best=5)}
     for name, fn in runs.items():
         if name not in args.modes.split(","):
             continue
