@@ -42,6 +42,26 @@ class capgen_param_info(C.Structure):
 
 
 _P = C.c_void_p
+
+
+class capgen_attn_geom(C.Structure):
+    """capgen_attn_geom_t (include/capgen.h): one attention launch's geometry for capgen_debug_attention_geom"""
+    _fields_ = [
+        ("B", C.c_int32), ("H", C.c_int32), ("Lq", C.c_int32), ("Lk", C.c_int32), ("dk", C.c_int32),
+        ("q", _P), ("q_ld", C.c_int64), ("q_bs", C.c_int64),
+        ("k", _P), ("k_ld", C.c_int64), ("k_bs", C.c_int64),
+        ("v", _P), ("v_ld", C.c_int64), ("v_bs", C.c_int64),
+        ("o_ld", C.c_int64), ("o_bs", C.c_int64),
+        ("kv_bmod", C.c_int32),
+        ("kv_row", _P), ("kv_row_ld", C.c_int64),
+        ("key_valid", _P), ("kv_bs", C.c_int64),
+        ("key_ids", _P), ("kid_bs", C.c_int64), ("pad_idx", C.c_int32),
+        ("causal", C.c_int32), ("q_pos0", C.c_int32),
+        ("temperature", C.c_float),
+        ("drop_p", C.c_float), ("drop_site", C.c_int32), ("drop_seed", C.c_uint64),
+    ]
+
+
 _SIGS = {
     "capgen_last_error": (C.c_char_p, []),
     "capgen_abi_version": (C.c_int, []),
@@ -100,9 +120,13 @@ _SIGS = {
     "capgen_debug_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
                                          C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
     "capgen_debug_attention_bwd_wo": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P,
-                                                _P, _P, _P, _P]),
-    "capgen_debug_qkv_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
-    "capgen_debug_cross_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+                                                _P, _P, _P, C.c_float, C.c_int, C.c_uint64, _P]),
+    "capgen_debug_qkv_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int,
+                                             C.c_float, C.c_int, C.c_uint64, _P]),
+    "capgen_debug_cross_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_float,
+                                               C.c_int, C.c_uint64, _P]),
+    "capgen_debug_attention_geom": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "capgen_debug_attention_head_mean": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "capgen_debug_layernorm_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, C.c_float, C.c_int, C.c_uint64, _P, _P,
                                              C.c_int, _P, _P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P]),
     "capgen_debug_layernorm_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int, _P,
@@ -178,6 +202,20 @@ _SIGS = {
 }
 EXPORTED = tuple(_SIGS)
 
+# the front hooks that gained `drop_p, drop_site, drop_seed` in front of `stream`: a call written for the
+# former signature (three arguments fewer) still works through this binding and means dropout off
+_DROP_HOOKS = ("capgen_debug_qkv_attention", "capgen_debug_cross_attention", "capgen_debug_attention_bwd_wo")
+
+
+def _with_default_drop(fn, nargs):
+    def hook(*args):
+        if len(args) == nargs - 3:
+            args = args[:-1] + (0.0, 0, 0) + args[-1:]
+        return fn(*args)
+    hook.__name__, hook.argtypes, hook.restype = fn.__name__, fn.argtypes, fn.restype
+    return hook
+
+
 _lib = None
 
 
@@ -196,6 +234,8 @@ def load():
         fn.argtypes = args
     if lib.capgen_abi_version() != ABI_VERSION:
         raise ImportError("capgen: libcapgen.so ABI version mismatch")
+    for name in _DROP_HOOKS:
+        setattr(lib, name, _with_default_drop(getattr(lib, name), len(_SIGS[name][1])))
     _lib = lib
     return lib
 

@@ -31,6 +31,9 @@ void attention_fwd(const AttnGeom& g, void* o, float* probs, DType t, hipStream_
 // dq/dk/dv mirror the q/k/v layouts (same ld/bs).  dO uses o_ld/o_bs.
 void attention_bwd(const AttnGeom& g, const float* probs, const void* dout, void* dq, void* dk,
                    void* dv, DType t, hipStream_t s);
+// LDS bytes the backward launch of g needs (0: the MFMA backward, whose LDS is static); attention_bwd
+// refuses more than 160 KB
+size_t attention_bwd_lds(const AttnGeom& g, DType t);
 // bf16 MFMA kernels (attention_mfma.hip), used by attention_fwd/bwd when attention_mfma_ok(g);
 // the backward recomputes the probabilities and never reads `probs`
 bool attention_mfma_ok(const AttnGeom& g);

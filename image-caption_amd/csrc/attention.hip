@@ -622,6 +622,10 @@ void attention_fwd(const AttnGeom& g, void* o, float* probs, DType t, hipStream_
   CAPGEN_HIP(hipGetLastError());
 }
 
+size_t attention_bwd_lds(const AttnGeom& g, DType t) {
+  return t == DType::BF16 && attention_mfma_ok(g) ? 0 : bwd_smem(g);
+}
+
 void attention_bwd(const AttnGeom& g, const float* probs, const void* dout, void* dq, void* dk, void* dv, DType t,
                    hipStream_t s) {
   if (skip_mask() & 8) return;

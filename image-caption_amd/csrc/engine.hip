@@ -2737,94 +2737,6 @@ int capgen_scst_rewards(const int64_t* target, int64_t target_ld, const int64_t*
   });
 }
 
-int capgen_debug_attention(int dtype, int B, int H, int Lq, int Lk, int dk, const void* q, const void* k,
-                           const void* v, const unsigned char* key_valid, int causal, float temperature, void* o,
-                           float* probs, const void* dout, void* dq, void* dk_, void* dv, void* stream) {
-  return guarded([&] {
-    require(B >= 1 && H >= 1 && dk >= 1, "debug_attention: bad shape");
-    const int64_t ld = (int64_t)H * dk;
-    AttnGeom g = attn_dense(B, H, Lq, Lk, dk, q, ld, k, ld, v, ld, ld);
-    g.key_valid = key_valid, g.kv_bs = Lk;
-    g.causal = causal;
-    g.temperature = temperature;
-    hipStream_t s = (hipStream_t)stream;
-    attention_fwd(g, o, probs, dt(dtype), s);
-    if (dout) attention_bwd(g, probs, dout, dq, dk_, dv, dt(dtype), s);
-  });
-}
-
-// the test hooks' weights in the fronts' tiled layout (a per-process scratch, grown as needed)
-static const bf16* debug_tiles(const bf16* W, int rows, hipStream_t s) {
-  static bf16* buf = nullptr;
-  static size_t cap = 0;
-  const size_t need = (size_t)rows * 512 * 2;
-  if (need > cap) {
-    CAPGEN_HIP(hipDeviceSynchronize());  // (the previous scratch may still be read)
-    if (buf) CAPGEN_HIP(hipFree(buf));
-    CAPGEN_HIP(hipMalloc(&buf, need));
-    cap = need;
-  }
-  qkv_tile_weights(W, rows, 512, buf, s);
-  return buf;
-}
-
-int capgen_debug_qkv_attention(int B, int L, int H, const void* X, const void* W, void* qkv, void* o,
-                               const unsigned char* key_valid, const int32_t* key_ids, int pad_idx, int causal,
-                               void* stream) {
-  return guarded([&] {
-    require(B >= 1 && L >= 1 && H >= 1, "debug_qkv_attention: bad shape");
-    const int d = H * 64;
-    QkvAttn qa;
-    AttnGeom& g = qa.g;
-    g = attn_dense(B, H, L, L, 64, qkv, 3 * d, (const bf16*)qkv + d, 3 * d, (const bf16*)qkv + 2 * d, 3 * d, d);
-    g.key_valid = key_valid, g.kv_bs = L, g.key_ids = key_ids, g.kid_bs = L, g.pad_idx = pad_idx, g.causal = causal;
-    qa.X = (const bf16*)X, qa.ldx = d, qa.W = debug_tiles((const bf16*)W, 3 * d, (hipStream_t)stream), qa.d = d;
-    qa.qkv = (bf16*)qkv, qa.ldqkv = 3 * d, qa.o = (bf16*)o;
-    qkv_attn_fwd(qa, (hipStream_t)stream);
-  });
-}
-
-int capgen_debug_cross_attention(int B, int Lq, int Lk, int H, const void* X, const void* Wq, const void* KV, void* q,
-                                 void* o, const unsigned char* key_valid, void* stream) {
-  return guarded([&] {
-    require(B >= 1 && Lq >= 1 && Lk >= 1 && H >= 1, "debug_cross_attention: bad shape");
-    const int d = H * 64;
-    QkvAttn qa;
-    qa.g = attn_dense(B, H, Lq, Lk, 64, q, d, KV, 2 * d, (const bf16*)KV + d, 2 * d, d);
-    qa.g.key_valid = key_valid, qa.g.kv_bs = Lk;
-    qa.cross = 1;
-    qa.X = (const bf16*)X, qa.ldx = d, qa.W = debug_tiles((const bf16*)Wq, d, (hipStream_t)stream), qa.d = d;
-    qa.qkv = (bf16*)q, qa.ldqkv = d, qa.o = (bf16*)o;
-    qkv_attn_fwd(qa, (hipStream_t)stream);
-  });
-}
-
-int capgen_debug_attention_bwd_wo(int B, int Lq, int Lk, int H, const void* q, const void* k, const void* v,
-                                  const unsigned char* key_valid, int causal, const void* dA, const void* Wo, void* dq,
-                                  void* dk, void* dv, void* stream) {
-  return guarded([&] {
-    require(B >= 1 && Lq >= 1 && Lk >= 1 && H * 64 == 512, "debug_attention_bwd_wo: bad shape (H * 64 = 512)");
-    const int d = H * 64;
-    const hipStream_t s = (hipStream_t)stream;
-    static bf16* wt = nullptr;  // (the test hook's tiled Wo^T scratch)
-    if (!wt) CAPGEN_HIP(hipMalloc(&wt, (size_t)512 * 512 * 2));
-    qkv_tile_weights_t((const bf16*)Wo, 512, wt, s);
-    QkvBwd qb;
-    AttnGeom& g = qb.g;
-    g = attn_dense(B, H, Lq, Lk, 64, q, d, k, d, v, d, d);
-    if (key_valid) g.key_valid = key_valid, g.kv_bs = Lk;
-    g.causal = causal;
-    qb.dA = (const bf16*)dA, qb.ldda = d, qb.Wt = wt;
-    qb.dq = (bf16*)dq, qb.dk = (bf16*)dk, qb.dv = (bf16*)dv;
-    qkv_attn_bwd(qb, s);
-  });
-}
-
-int capgen_debug_gemm_variant(int v) {
-  return guarded([&] { gemm_set_variant(v); });
-}
-
-// ---- test hooks of the row-wise / loss / Adam / selection / SCST launchers (ops.h, rl.h) ----
 namespace {
 // the dropout descriptor of a hook: p <= 0 is dropout off; otherwise the 64-bit seed goes to a
 // device word (as the engine's step seed) that lives until the launch has run
@@ -2852,6 +2764,152 @@ struct HookDrop {
 };
 }  // namespace
 
+int capgen_debug_attention(int dtype, int B, int H, int Lq, int Lk, int dk, const void* q, const void* k,
+                           const void* v, const unsigned char* key_valid, int causal, float temperature, void* o,
+                           float* probs, const void* dout, void* dq, void* dk_, void* dv, void* stream) {
+  return guarded([&] {
+    require(B >= 1 && H >= 1 && dk >= 1, "debug_attention: bad shape");
+    const int64_t ld = (int64_t)H * dk;
+    AttnGeom g = attn_dense(B, H, Lq, Lk, dk, q, ld, k, ld, v, ld, ld);
+    g.key_valid = key_valid, g.kv_bs = Lk;
+    g.causal = causal;
+    g.temperature = temperature;
+    hipStream_t s = (hipStream_t)stream;
+    attention_fwd(g, o, probs, dt(dtype), s);
+    if (dout) attention_bwd(g, probs, dout, dq, dk_, dv, dt(dtype), s);
+  });
+}
+
+int capgen_debug_attention_geom(int dtype, const capgen_attn_geom_t* c, void* o, float* probs, const void* dout,
+                                void* dq, void* dk_, void* dv, void* stream) {
+  return guarded([&] {
+    require(c != nullptr, "debug_attention_geom: no geometry");
+    require(c->B >= 1 && c->H >= 1 && c->dk >= 1 && c->Lq >= 1 && c->Lq <= 64 && c->Lk >= 1 && c->Lk <= 64,
+            "debug_attention_geom: bad shape (B, H, dk >= 1; Lq, Lk in [1, 64])");
+    require(o && c->q && c->k && c->v, "debug_attention_geom: q, k, v and o are required");
+    require(!c->kv_row || c->kv_row_ld >= c->Lk, "debug_attention_geom: kv_row_ld < Lk");
+    const hipStream_t s = (hipStream_t)stream;
+    HookDrop hd(c->drop_p, c->drop_site, c->drop_seed, s);
+    AttnGeom g;
+    g.B = c->B, g.H = c->H, g.Lq = c->Lq, g.Lk = c->Lk, g.dk = c->dk;
+    g.q = c->q, g.q_ld = c->q_ld, g.q_bs = c->q_bs;
+    g.k = c->k, g.k_ld = c->k_ld, g.k_bs = c->k_bs;
+    g.v = c->v, g.v_ld = c->v_ld, g.v_bs = c->v_bs;
+    g.o_ld = c->o_ld, g.o_bs = c->o_bs;
+    g.kv_bmod = c->kv_bmod;
+    g.kv_row = c->kv_row, g.kv_row_ld = c->kv_row_ld;
+    g.key_valid = c->key_valid, g.kv_bs = c->kv_bs;
+    g.key_ids = c->key_ids, g.kid_bs = c->kid_bs, g.pad_idx = c->pad_idx;
+    g.causal = c->causal, g.q_pos0 = c->q_pos0;
+    g.temperature = c->temperature;
+    g.drop = hd.d;
+    if (dout) {
+      // (the backward kernels write dk / dv per query batch and know no row table)
+      require(dq && dk_ && dv, "debug_attention_geom: dout needs dq, dk, dv");
+      require(!g.kv_row && g.kv_bmod == 0, "debug_attention_geom: no backward with kv_row / kv_bmod");
+      require(probs || (dt(dtype) == DType::BF16 && attention_mfma_ok(g)),
+              "debug_attention_geom: this backward reads the saved probs");
+      // (a backward the launcher would refuse is refused here, before the forward: nothing is launched)
+      require(attention_bwd_lds(g, dt(dtype)) <= 160 * 1024,
+              "debug_attention_geom: attention_bwd: LDS budget exceeded (head size too large)");
+    }
+    attention_fwd(g, o, probs, dt(dtype), s);
+    if (dout) attention_bwd(g, probs, dout, dq, dk_, dv, dt(dtype), s);
+    hd.finish(s);
+  });
+}
+
+int capgen_debug_attention_head_mean(const float* probs, int B, int H, int Lq, int Lk, int row, float* out,
+                                     void* stream) {
+  return guarded([&] {
+    require(B >= 1 && H >= 1 && Lq >= 1 && Lk >= 1 && row >= 0 && row < Lq, "debug_attention_head_mean: bad shape");
+    require(probs && out, "debug_attention_head_mean: probs and out are required");
+    attention_head_mean(probs, B, H, Lq, Lk, row, out, (hipStream_t)stream);
+  });
+}
+
+// the test hooks' weights in the fronts' tiled layout (a per-process scratch, grown as needed)
+static const bf16* debug_tiles(const bf16* W, int rows, hipStream_t s) {
+  static bf16* buf = nullptr;
+  static size_t cap = 0;
+  const size_t need = (size_t)rows * 512 * 2;
+  if (need > cap) {
+    CAPGEN_HIP(hipDeviceSynchronize());  // (the previous scratch may still be read)
+    if (buf) CAPGEN_HIP(hipFree(buf));
+    CAPGEN_HIP(hipMalloc(&buf, need));
+    cap = need;
+  }
+  qkv_tile_weights(W, rows, 512, buf, s);
+  return buf;
+}
+
+int capgen_debug_qkv_attention(int B, int L, int H, const void* X, const void* W, void* qkv, void* o,
+                               const unsigned char* key_valid, const int32_t* key_ids, int pad_idx, int causal,
+                               float drop_p, int drop_site, uint64_t drop_seed, void* stream) {
+  return guarded([&] {
+    require(B >= 1 && L >= 1 && H >= 1, "debug_qkv_attention: bad shape");
+    const int d = H * 64;
+    HookDrop hd(drop_p, drop_site, drop_seed, (hipStream_t)stream);
+    QkvAttn qa;
+    AttnGeom& g = qa.g;
+    g = attn_dense(B, H, L, L, 64, qkv, 3 * d, (const bf16*)qkv + d, 3 * d, (const bf16*)qkv + 2 * d, 3 * d, d);
+    g.key_valid = key_valid, g.kv_bs = L, g.key_ids = key_ids, g.kid_bs = L, g.pad_idx = pad_idx, g.causal = causal;
+    qa.X = (const bf16*)X, qa.ldx = d, qa.W = debug_tiles((const bf16*)W, 3 * d, (hipStream_t)stream), qa.d = d;
+    qa.qkv = (bf16*)qkv, qa.ldqkv = 3 * d, qa.o = (bf16*)o;
+    g.drop = hd.d;
+    qkv_attn_fwd(qa, (hipStream_t)stream);
+    hd.finish((hipStream_t)stream);
+  });
+}
+
+int capgen_debug_cross_attention(int B, int Lq, int Lk, int H, const void* X, const void* Wq, const void* KV, void* q,
+                                 void* o, const unsigned char* key_valid, float drop_p, int drop_site,
+                                 uint64_t drop_seed, void* stream) {
+  return guarded([&] {
+    require(B >= 1 && Lq >= 1 && Lk >= 1 && H >= 1, "debug_cross_attention: bad shape");
+    const int d = H * 64;
+    HookDrop hd(drop_p, drop_site, drop_seed, (hipStream_t)stream);
+    QkvAttn qa;
+    qa.g = attn_dense(B, H, Lq, Lk, 64, q, d, KV, 2 * d, (const bf16*)KV + d, 2 * d, d);
+    qa.g.key_valid = key_valid, qa.g.kv_bs = Lk;
+    qa.cross = 1;
+    qa.X = (const bf16*)X, qa.ldx = d, qa.W = debug_tiles((const bf16*)Wq, d, (hipStream_t)stream), qa.d = d;
+    qa.qkv = (bf16*)q, qa.ldqkv = d, qa.o = (bf16*)o;
+    qa.g.drop = hd.d;
+    qkv_attn_fwd(qa, (hipStream_t)stream);
+    hd.finish((hipStream_t)stream);
+  });
+}
+
+int capgen_debug_attention_bwd_wo(int B, int Lq, int Lk, int H, const void* q, const void* k, const void* v,
+                                  const unsigned char* key_valid, int causal, const void* dA, const void* Wo, void* dq,
+                                  void* dk, void* dv, float drop_p, int drop_site, uint64_t drop_seed, void* stream) {
+  return guarded([&] {
+    require(B >= 1 && Lq >= 1 && Lk >= 1 && H * 64 == 512, "debug_attention_bwd_wo: bad shape (H * 64 = 512)");
+    const int d = H * 64;
+    const hipStream_t s = (hipStream_t)stream;
+    HookDrop hd(drop_p, drop_site, drop_seed, s);
+    static bf16* wt = nullptr;  // (the test hook's tiled Wo^T scratch)
+    if (!wt) CAPGEN_HIP(hipMalloc(&wt, (size_t)512 * 512 * 2));
+    qkv_tile_weights_t((const bf16*)Wo, 512, wt, s);
+    QkvBwd qb;
+    AttnGeom& g = qb.g;
+    g = attn_dense(B, H, Lq, Lk, 64, q, d, k, d, v, d, d);
+    if (key_valid) g.key_valid = key_valid, g.kv_bs = Lk;
+    g.causal = causal;
+    qb.dA = (const bf16*)dA, qb.ldda = d, qb.Wt = wt;
+    qb.dq = (bf16*)dq, qb.dk = (bf16*)dk, qb.dv = (bf16*)dv;
+    g.drop = hd.d;
+    qkv_attn_bwd(qb, s);
+    hd.finish(s);
+  });
+}
+
+int capgen_debug_gemm_variant(int v) {
+  return guarded([&] { gemm_set_variant(v); });
+}
+
+// ---- test hooks of the row-wise / loss / Adam / selection / SCST launchers (ops.h, rl.h) ----
 int capgen_debug_layernorm_fwd(int dtype, int M, int d, const void* a, const float* a_bias, float drop_p,
                                int drop_site, uint64_t drop_seed, const void* res, const float* pe, int pe_L,
                                const float* gamma, const float* beta, const int32_t* ids, int64_t ids_ld, int pad_idx,

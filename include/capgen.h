@@ -323,19 +323,55 @@ int capgen_debug_attention(int dtype, int B, int H, int Lq, int Lk, int dk, cons
                            const void* v, const unsigned char* key_valid, int causal, float temperature, void* o,
                            float* probs, const void* dout, void* dq, void* dk_, void* dv, void* stream);
 
+/* Test hook: one attention launch in any geometry the engine uses (csrc/attention.h AttnGeom, field by
+ * field but for its scheduling members): row (b, i) of head h lives at base + b*bs + i*ld + h*dk (elements
+ * of dtype); dq / dk / dv mirror q / k / v, dout mirrors o.  kv_bmod > 0: K / V / key_valid of query batch
+ * b come from batch b % kv_bmod.  kv_row (Lq = 1 or the VALU forward): key j of batch b is stored in batch
+ * kv_row[b*kv_row_ld + j], an absolute row of the K / V buffer.  Masks: key_valid[b*kv_bs + j] == 0,
+ * key_ids[b*kid_bs + j] == pad_idx, causal keys j > q_pos0 + i.  drop_p <= 0 = no dropout, else as the
+ * LayerNorm hooks below (element index ((b*H + h)*Lq + i)*Lk + j).  tests/test_gpu_attention.py compares
+ * every kernel this reaches with the float64 restatement tests/attention_ref.py. */
+typedef struct capgen_attn_geom {
+  int32_t B, H, Lq, Lk, dk;
+  const void* q; int64_t q_ld, q_bs;
+  const void* k; int64_t k_ld, k_bs;
+  const void* v; int64_t v_ld, v_bs;
+  int64_t o_ld, o_bs;
+  int32_t kv_bmod;
+  const int32_t* kv_row; int64_t kv_row_ld;
+  const unsigned char* key_valid; int64_t kv_bs;
+  const int32_t* key_ids; int64_t kid_bs; int32_t pad_idx;
+  int32_t causal, q_pos0;
+  float temperature;
+  float drop_p; int32_t drop_site; uint64_t drop_seed;
+} capgen_attn_geom_t;
+/* attention_fwd into o (and probs [B,H,Lq,Lk] f32, pre-dropout, optional), then attention_bwd when
+ * dout != NULL (no kv_row / kv_bmod there; the f32 and head-size != 64 backward reads probs).  A backward
+ * the launcher refuses (its LDS need over 160 KB) is an error before anything is launched. */
+int capgen_debug_attention_geom(int dtype, const capgen_attn_geom_t* g, void* o, float* probs, const void* dout,
+                                void* dq, void* dk, void* dv, void* stream);
+/* out[b*Lk + j] = mean over heads of probs[b, :, row, j] (attention_head_mean). */
+int capgen_debug_attention_head_mean(const float* probs, int B, int H, int Lq, int Lk, int row, float* out,
+                                     void* stream);
+
+/* The three hooks of the fused fronts below take the attention dropout as the LayerNorm hooks do:
+ * drop_p <= 0 = off, else drop_seed goes to a device word for the launch.  (These test hooks gained the
+ * three arguments without a change of CAPGEN_ABI_VERSION: no entry outside the test hooks changed.) */
+
 /* Test hook: the fused self-attention front (qkv_attn.hip; modules.py:67-76 then 16-27), bf16:
  * qkv [B*L, 3*H*64] = X [B*L, H*64] . W^T (W = [q; k; v] weights [3*H*64, H*64]), then the masked
  * attention of every (image, head) into o [B*L, H*64].  key_valid [B][L] bytes / key_ids [B][L]
  * int32 (== pad_idx: masked) optional; causal masks keys j > i.  Head size 64, H*64 = 512 only. */
 int capgen_debug_qkv_attention(int B, int L, int H, const void* X, const void* W, void* qkv, void* o,
                                const unsigned char* key_valid, const int32_t* key_ids, int pad_idx, int causal,
-                               void* stream);
+                               float drop_p, int drop_site, uint64_t drop_seed, void* stream);
 
 /* Test hook: the fused cross-attention front (qkv_attn.hip cross mode; modules.py:195-197), bf16:
  * q [B*Lq, H*64] = X . Wq^T, then attention over K / V = KV [B*Lk, 2*H*64] (k | v per row) with the
  * key mask key_valid [B][Lk] (optional) into o [B*Lq, H*64].  Head size 64, H*64 = 512 only. */
 int capgen_debug_cross_attention(int B, int Lq, int Lk, int H, const void* X, const void* Wq, const void* KV, void* q,
-                                 void* o, const unsigned char* key_valid, void* stream);
+                                 void* o, const unsigned char* key_valid, float drop_p, int drop_site,
+                                 uint64_t drop_seed, void* stream);
 
 /* Test hook: the fused output side of an attention block's backward (qkv_attn.hip qkv_attn_bwd;
  * modules.py:77 o_linear + 16-27), bf16: dO = dA . Wo (dA [B*Lq, 512], Wo [512, 512] nn.Linear), then
@@ -343,7 +379,7 @@ int capgen_debug_cross_attention(int B, int Lq, int Lk, int H, const void* X, co
  * optional, causal) into dq / dk / dv.  Head size 64, H * 64 = 512. */
 int capgen_debug_attention_bwd_wo(int B, int Lq, int Lk, int H, const void* q, const void* k, const void* v,
                                   const unsigned char* key_valid, int causal, const void* dA, const void* Wo, void* dq,
-                                  void* dk, void* dv, void* stream);
+                                  void* dk, void* dv, float drop_p, int drop_site, uint64_t drop_seed, void* stream);
 
 /* Test hooks: the row-wise, loss, optimizer, selection and SCST launchers (csrc/ops.h, csrc/select.h, csrc/rl.h),
  * one launcher per call on raw device pointers and the given stream; the arguments are the

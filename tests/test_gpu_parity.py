@@ -1238,7 +1238,7 @@ def test_fused_attention_bwd_wo_vs_separate(B, Lq, Lk, mask):
         if fused:
             _lib.check(lib.capgen_debug_attention_bwd_wo(B, Lq, Lk, H, ptr(qd), ptr(kd), ptr(vd),
                                                          ptr(vald) if mask == "valid" else None, causal, ptr(dAd),
-                                                         ptr(Wod), ptr(dq), ptr(dk), ptr(dv), None))
+                                                         ptr(Wod), ptr(dq), ptr(dk), ptr(dv), 0, 0, 0, None))
         else:
             dO = torch.empty(B * Lq, d, device=DEV, dtype=torch.bfloat16)
             o = torch.empty(B * Lq, d, device=DEV, dtype=torch.bfloat16)
@@ -1301,7 +1301,7 @@ def test_fused_qkv_attention_vs_torch(B, L, mask):
         Xd, Wd, KVd, vd = X.to(DEV), Wq.to(DEV), KV.to(DEV), kvalid.to(DEV)
         ptr = lambda t: C.c_void_p(t.data_ptr())
         _lib.check(lib.capgen_debug_cross_attention(B, L, Lk, H, ptr(Xd), ptr(Wd), ptr(KVd), ptr(qd), ptr(o), ptr(vd),
-                                                    None))
+                                                    0, 0, 0, None))
         torch.cuda.synchronize()
         ulp = (q_ref.abs() * 2.0 ** -7).clamp_min(1e-5)
         assert ((qd.float().cpu() - q_ref).abs() <= ulp).all()
@@ -1334,7 +1334,7 @@ def test_fused_qkv_attention_vs_torch(B, L, mask):
     _lib.check(lib.capgen_debug_qkv_attention(B, L, H, ptr(Xd), ptr(Wd), ptr(qkv), ptr(o),
                                               ptr(vd) if mask == "valid_causal" else None,
                                               ptr(idd) if mask == "ids_causal" else None, 0,
-                                              int(mask != "none"), None))
+                                              int(mask != "none"), 0, 0, 0, None))
     torch.cuda.synchronize()
     got = qkv.float().cpu()
     # each element: the bf16 rounding of the f32 product, or its neighbour (summation-order tie)

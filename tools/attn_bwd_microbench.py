@@ -30,7 +30,7 @@ def main():
         valid = torch.ones(B, Lk, dtype=torch.uint8, device=dev)
         for _ in range(reps):
             lib.capgen_debug_attention_bwd_wo(B, Lq, Lk, H, p(q), p(k), p(v), p(valid), causal, p(dA), p(Wo), p(dq),
-                                              p(dk), p(dv), None)
+                                              p(dk), p(dv), 0, 0, 0, None)
         for _ in range(reps):
             # dO = dA . Wo  (NN: B operand transposed)
             lib.capgen_debug_gemm(B * Lq, d, d, p(dA), d, 0, p(Wo), d, 1, p(dO), d, 1, 1, None, 1.0, 0, 0, None)

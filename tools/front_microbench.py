@@ -49,7 +49,7 @@ def main():
             q = torch.empty(B * L, d, device=dev, dtype=torch.bfloat16)
             valid = torch.ones(B, Lk, dtype=torch.uint8, device=dev)
             Wq = W[:d].contiguous()
-            fused = lambda: lib.capgen_debug_cross_attention(B, L, Lk, H, p(X), p(Wq), p(KV), p(q), p(o), p(valid), None)
+            fused = lambda: lib.capgen_debug_cross_attention(B, L, Lk, H, p(X), p(Wq), p(KV), p(q), p(o), p(valid), 0, 0, 0, None)
             k = torch.randn(B * Lk, d, generator=g).to(torch.bfloat16).to(dev)  # (packed copies: the hook
             v = torch.randn(B * Lk, d, generator=g).to(torch.bfloat16).to(dev)  # takes row stride H * 64)
 
@@ -59,7 +59,7 @@ def main():
                                            None, None, None, None)
         else:
             ids = torch.randint(3, 100, (B, L), generator=g, dtype=torch.int32).to(dev)
-            fused = lambda: lib.capgen_debug_qkv_attention(B, L, H, p(X), p(W), p(qkv), p(o), None, p(ids), 0, 1, None)
+            fused = lambda: lib.capgen_debug_qkv_attention(B, L, H, p(X), p(W), p(qkv), p(o), None, p(ids), 0, 1, 0, 0, 0, None)
             # (the attention hook takes packed [B, L, H * 64] tensors: separate buffers of the same size)
             qv, kv_, vv = (torch.randn(B * L, d, generator=g).to(torch.bfloat16).to(dev) for _ in range(3))
 
