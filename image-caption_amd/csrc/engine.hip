@@ -835,19 +835,28 @@ struct capgen_engine {
   void ensure_acts(int B, int N, int T) {
     if (ws && B <= a.B && N <= a.N && T <= a.T) return;
     int nB = std::max(B, a.B), nN = std::max(N, a.N), nT = std::max(T, a.T);
-    if (ws) {
+    if (ws) {  // the graphs hold the old block's addresses
       hz::host_sync(es);
-      CAPGEN_HIP(hipFree(ws));
-      ws = nullptr;
       drop_graph();
     }
-    Planner p;
-    plan_acts(p, nB, nN, nT);
-    CAPGEN_HIP(hipMalloc(&ws, p.used));
-    Planner q;
-    q.base = (char*)ws;
-    plan_acts(q, nB, nN, nT);
+    replan(ws, [&](Planner& p) { plan_acts(p, nB, nN, nT); });
     a.B = nB, a.N = nN, a.T = nT;
+  }
+  // (re)allocate a workspace block: plan(p) lays its buffers out on p, once without a base for the size
+  // and once over the new block for the pointers
+  template <class F>
+  void replan(void*& block, F&& plan) {
+    if (block) {
+      hz::host_sync(es);
+      CAPGEN_HIP(hipFree(block));
+      block = nullptr;
+    }
+    Planner p;
+    plan(p);
+    CAPGEN_HIP(hipMalloc(&block, p.used));
+    Planner q;
+    q.base = (char*)block;
+    plan(q);
   }
 
   void drop_graph() {
@@ -1752,7 +1761,6 @@ struct capgen_engine {
   // results of every kernel are independent of how many rows/positions are in the launch.
   void encode_only(const void* feats, DType ft, const float* pos, int B, int N, hipStream_t s) {
     const int Me = B * N, d = L.d;
-    ensure_acts(B, N, 2);
     pack_encoder_input(feats, ft, pos, Me, L.F, L.P, L.Kp, a.Aenc, act, a.valid, s);
     if (L.has_img) image_objects_fwd(B, N, false, s);
     else enc_embed_fwd(Me, /*keep=*/false, s);
@@ -1799,18 +1807,17 @@ struct capgen_engine {
   void ensure_gen(int R, int N) {
     if (gws && R <= g.R && N <= g.N) return;
     int nR = std::max(R, g.R), nN = std::max(N, g.N);
-    if (gws) {
-      hz::host_sync(es);
-      CAPGEN_HIP(hipFree(gws));
-      gws = nullptr;
-    }
-    Planner p;
-    plan_gen(p, nR, nN);
-    CAPGEN_HIP(hipMalloc(&gws, p.used));
-    Planner q;
-    q.base = (char*)gws;
-    plan_gen(q, nR, nN);
+    replan(gws, [&](Planner& p) { plan_gen(p, nR, nN); });
     g.R = nR, g.N = nN;
+  }
+  // What greedy, beam_run and sample do first, for B images and R decoder rows.  The order matters: every
+  // allocation before anything is enqueued, the decode tiles built after the encoder has run
+  void begin_decode(const void* feats, DType ft, const float* pos, int B, int N, int R, hipStream_t s) {
+    ensure_acts(B, N, 2);
+    ensure_gen(R, N);
+    ensure_dtiles();
+    encode_only(feats, ft, pos, B, N, s);
+    build_dtiles(s);
   }
 
   // decoder for position t of R rows (rows r -> image r % Bimg); tokens = ids[:, t].
@@ -1833,17 +1840,24 @@ struct capgen_engine {
       if (!DT(w.Wqkv) || !DT(w.Wq_c) || !DT(w.W1)) return 0;
     return decode_ln_fold == 2 || M < 1024 ? 2 : 1;
   }
-  // one decode Linear: C (+)= X . W^T (+ bias) (ReLU); lng: the A rows are LayerNorm inputs, normalised
-  // with (lng, lnb) and the row mask rm inside the GEMM, the normalised rows stored into lny
+  // one decode Linear: C = X . W^T (+ bias) (ReLU), C's row stride ldc (0: N).  ln: X is the output of
+  // that LayerNorm: its own launch in front of the GEMM, or (fold) the GEMM reads the LayerNorm's input
+  // and residual, normalises the rows itself and stores them into X (= ln->y).  C2: the columns from
+  // ldc on go to C2 (row stride ldc2)
   void dec_linear(const void* X, int64_t woff, int M, int N, int K, void* C, const float* bias, int relu,
-                  hipStream_t s, const void* lnres = nullptr, const float* lng = nullptr, const float* lnb = nullptr,
-                  void* lny = nullptr, const RowMask* rm = nullptr) {
+                  hipStream_t s, const LnFwd* ln = nullptr, bool fold = false, int64_t ldc = 0, void* C2 = nullptr,
+                  int64_t ldc2 = 0) {
     GemmArgs ga;
-    ga.M = M, ga.N = N, ga.K = K, ga.A = X, ga.lda = K, ga.B = W(woff), ga.ldb = K, ga.C = C, ga.ldc = N;
+    ga.M = M, ga.N = N, ga.K = K, ga.A = X, ga.lda = K, ga.B = W(woff), ga.ldb = K, ga.C = C, ga.ldc = ldc ? ldc : N;
     ga.bt = DT(woff), ga.bias = bias, ga.relu = relu, ga.prio = prio(s);
-    ga.ln_res = lnres, ga.ln_gamma = lng, ga.ln_beta = lnb, ga.ln_y = lny;
-    if (rm) ga.ln_ids = rm->ids, ga.ln_ids_ld = rm->ids_ld, ga.ln_pad = rm->pad_idx;
-    if (stamp_on) ga.stamp = stamp(s, std::string(lng ? "gemm fwd+ln " : "gemm fwd ") + dims(M, N, K));
+    if (C2) ga.C2 = C2, ga.ldc2 = ldc2, ga.nsplit = (int)ldc;
+    if (ln && fold) {
+      ga.A = ln->a, ga.ln_res = ln->res, ga.ln_gamma = ln->gamma, ga.ln_beta = ln->beta, ga.ln_y = ln->y;
+      if (ln->mask.ids) ga.ln_ids = ln->mask.ids, ga.ln_ids_ld = ln->mask.ids_ld, ga.ln_pad = ln->mask.pad_idx;
+    } else if (ln) {
+      lnf(*ln, s);
+    }
+    if (stamp_on) ga.stamp = stamp(s, std::string(ga.ln_gamma ? "gemm fwd+ln " : "gemm fwd ") + dims(M, N, K));
     gemm(ga, act, act, false, false, s);
   }
 
@@ -1859,37 +1873,27 @@ struct capgen_engine {
       gemm(ge, act, act, false, false, s);
     } else {
       embedding_gather(P(L.emb), ids + t, Tc, R, L.dwe, g.E, act, s, L.V);
-      linear(g.E, L.dwe, L.Wel, L.dwe, g.tmp, dd, act, R, dd, L.dwe, nullptr, 0, s, DT(L.Wel));
+      dec_linear(g.E, L.Wel, R, dd, L.dwe, g.tmp, nullptr, 0, s);
     }
-    LnFwd ln;
-    ln.M = R, ln.d = dd, ln.a = g.tmp, ln.pe = pe + (int64_t)t * dd, ln.pe_L = 1, ln.gamma = P(L.dec_lng);
-    ln.beta = P(L.dec_lnb), ln.y = g.x;
-    lnf(ln, s);
+    // ln: the LayerNorm whose output g.x the next QKV projection reads: the embedding's (position t of
+    // the PE table; never folded), then each block's FFN LayerNorm
+    LnFwd ln = ln_fwd(dec_embed_site(R), g.tmp, nullptr, g.x, false);
+    ln.pe = pe + (int64_t)t * dd, ln.pe_L = 1;
     RowMask rm{};
     rm.ids = ids + t, rm.ids_ld = Tc, rm.pad_idx = cfg.pad_idx;
     const int64_t cld = (int64_t)Tc * 2 * dd;
+    // which LayerNorms run inside the GEMM that reads them: every site of a block / the cross-query site
     const int fmode = ln_fold(R);
-    const bool fold = fmode == 2, fold1 = fmode >= 1;  // every site / the cross-query site
+    const bool fold = fmode == 2, fold1 = fmode >= 1;
     for (int l = 0; l < L.Ld; ++l) {
       const auto& w = L.dec[l];
       void* cl = at(cache, (int64_t)l * R * cld);
-      if (act == DType::BF16) {  // one GEMM: Q columns -> g.q, K/V columns -> the cache at position t
-        GemmArgs ga;
-        ga.M = R, ga.N = 3 * dd, ga.K = dd, ga.A = g.x, ga.lda = dd, ga.B = W(w.Wqkv), ga.ldb = dd;
-        ga.C = g.q, ga.ldc = dd, ga.C2 = at(cl, (int64_t)t * 2 * dd), ga.ldc2 = cld, ga.nsplit = dd;
-        ga.bt = DT(w.Wqkv);
-        if (fold && l > 0) {  // the previous block's FFN LayerNorm (W2 output in tmp + x2) -> g.x
-          const auto& wp = L.dec[l - 1];
-          ga.A = g.tmp, ga.ln_res = g.x2, ga.ln_gamma = P(wp.lfg), ga.ln_beta = P(wp.lfb), ga.ln_y = g.x;
-          ga.ln_ids = rm.ids, ga.ln_ids_ld = rm.ids_ld, ga.ln_pad = rm.pad_idx;
-        }
-        ga.prio = prio(s);
-        if (stamp_on) ga.stamp = stamp(s, std::string(ga.ln_gamma ? "gemm fwd+ln " : "gemm fwd ") + dims(R, 3 * dd, dd));
-        gemm(ga, act, act, false, false, s);
+      void* kv = at(cl, (int64_t)t * 2 * dd);  // the cache at position t
+      if (act == DType::BF16) {  // one GEMM: Q columns -> g.q, K/V columns -> the cache
+        dec_linear(g.x, w.Wqkv, R, 3 * dd, dd, g.q, nullptr, 0, s, &ln, fold && l > 0, dd, kv, cld);
       } else {
-        linear(g.x, dd, w.Wqkv, dd, g.q, dd, act, R, dd, dd, nullptr, 0, s);
-        linear(g.x, dd, w.Wqkv + (int64_t)dd * dd, dd, at(cl, (int64_t)t * 2 * dd), cld, act, R, 2 * dd, dd, nullptr,
-               0, s);
+        dec_linear(g.x, w.Wqkv, R, dd, dd, g.q, nullptr, 0, s, &ln);
+        dec_linear(g.x, w.Wqkv + (int64_t)dd * dd, R, 2 * dd, dd, kv, nullptr, 0, s, nullptr, false, cld);
       }
       AttnGeom sg;
       sg.B = R, sg.H = Hd, sg.Lq = 1, sg.Lk = t + 1, sg.dk = dkd;
@@ -1901,16 +1905,9 @@ struct capgen_engine {
       sg.kv_row = kv_row, sg.kv_row_ld = Tc;
       sg.temperature = std::sqrt((float)dkd);
       attf(sg, g.att, nullptr, act, s);
-      if (fold1) {  // att . Wo_s^T into tmp; the cross-query GEMM normalises tmp + x (-> g.x1)
-        dec_linear(g.att, w.Wo_s, R, dd, dd, g.tmp, nullptr, 0, s);
-        dec_linear(g.tmp, w.Wq_c, R, dd, dd, g.q, nullptr, 0, s, g.x, P(w.lsg), P(w.lsb), g.x1);
-      } else {
-        linear(g.att, dd, w.Wo_s, dd, g.tmp, dd, act, R, dd, dd, nullptr, 0, s, DT(w.Wo_s));
-        LnFwd l1;
-        l1.M = R, l1.d = dd, l1.a = g.tmp, l1.res = g.x, l1.gamma = P(w.lsg), l1.beta = P(w.lsb), l1.y = g.x1;
-        lnf(l1, s);
-        linear(g.x1, dd, w.Wq_c, dd, g.q, dd, act, R, dd, dd, nullptr, 0, s, DT(w.Wq_c));
-      }
+      dec_linear(g.att, w.Wo_s, R, dd, dd, g.tmp, nullptr, 0, s);
+      const LnFwd ls = ln_fwd(dec_self_site(l, R, false), g.tmp, g.x, g.x1, false);
+      dec_linear(g.x1, w.Wq_c, R, dd, dd, g.q, nullptr, 0, s, &ls, fold1);
       const bool want_p = want_attn && l == L.Ld - 1;
       AttnGeom c = cross_kv(l, N);  // rows r -> image r % Bimg
       const int kb = R / Bimg;  // beam rows per image: row j * Bimg + b
@@ -1927,30 +1924,17 @@ struct capgen_engine {
         c.o_ld = dd, c.o_bs = dd;
       }
       attf(c, g.att, want_p ? g.Pc : nullptr, act, s);
-      if (fold) {  // att . Wo_c^T into tmp, the FFN's first GEMM normalises tmp + x1 (-> g.x2);
-                   // h . W2^T + b2 into tmp, normalised with x2 by the next block's QKV GEMM
-        dec_linear(g.att, w.Wo_c, R, dd, dd, g.tmp, nullptr, 0, s);
-        dec_linear(g.tmp, w.W1, R, L.fd, dd, g.h, P(w.b1), 1, s, g.x1, P(w.lcg), P(w.lcb), g.x2);
-        dec_linear(g.h, w.W2, R, dd, L.fd, g.tmp, P(w.b2), 0, s);
-        if (l == L.Ld - 1) {  // the last block's FFN LayerNorm feeds the classifier: its own launch
-          LnFwd l3;
-          l3.M = R, l3.d = dd, l3.a = g.tmp, l3.res = g.x2, l3.gamma = P(w.lfg), l3.beta = P(w.lfb);
-          l3.mask = rm, l3.y = g.x;
-          lnf(l3, s);
-        }
-        continue;
-      }
-      linear(g.att, dd, w.Wo_c, dd, g.tmp, dd, act, R, dd, dd, nullptr, 0, s, DT(w.Wo_c));
-      LnFwd l2;
-      l2.M = R, l2.d = dd, l2.a = g.tmp, l2.res = g.x1, l2.gamma = P(w.lcg), l2.beta = P(w.lcb), l2.y = g.x2;
-      lnf(l2, s);
-      linear(g.x2, dd, w.W1, dd, g.h, L.fd, act, R, L.fd, dd, P(w.b1), 1, s, DT(w.W1));
-      linear(g.h, L.fd, w.W2, L.fd, g.tmp, dd, act, R, dd, L.fd, nullptr, 0, s, DT(w.W2));
-      LnFwd l3;
-      l3.M = R, l3.d = dd, l3.a = g.tmp, l3.a_bias = P(w.b2), l3.res = g.x2, l3.gamma = P(w.lfg), l3.beta = P(w.lfb);
-      l3.mask = rm, l3.y = g.x;
-      lnf(l3, s);
+      dec_linear(g.att, w.Wo_c, R, dd, dd, g.tmp, nullptr, 0, s);
+      const LnFwd lc = ln_fwd(dec_cross_site(l, R, false), g.tmp, g.x1, g.x2, false);
+      dec_linear(g.x2, w.W1, R, L.fd, dd, g.h, P(w.b1), 1, s, &lc, fold);
+      // b2: a GEMM that normalises its A rows adds no bias to them, so where the FFN LayerNorm folds, the
+      // W2 GEMM adds b2 (also in the last block, so that every block rounds alike); else the LayerNorm does
+      dec_linear(g.h, w.W2, R, dd, L.fd, g.tmp, fold ? P(w.b2) : nullptr, 0, s);
+      ln = ln_fwd(dec_ffn_site(l, R, false), g.tmp, g.x2, g.x, false);
+      ln.mask = rm;  // the tokens of position t, not the training captions
+      if (fold) ln.a_bias = nullptr;
     }
+    lnf(ln, s);  // the last block's FFN LayerNorm feeds the classifier (or move-first): its own launch
     const void* xo = g.x;
     if (L.has_mf) {  // rows r -> image r % Bimg
       move_first_fwd(g.x, a.X[L.Le], R, 1, Bimg, N, g.x2, g.h, g.tmp, g.x1, /*keep=*/false, /*drop_on=*/false, s);
@@ -1980,11 +1964,7 @@ struct capgen_engine {
               hipStream_t s) {
     require(N >= 1 && N <= 64, "greedy: N must be in [1, 64]");
     require(B >= 1, "greedy: need B >= 1");
-    ensure_acts(B, N, 2);
-    ensure_gen(B, N);
-    ensure_dtiles();
-    encode_only(feats, ft, pos, B, N, s);
-    build_dtiles(s);
+    begin_decode(feats, ft, pos, B, N, B, s);
     const int Tc = L.maxlen, W = L.maxlen + 1;
     init_gen_ids(ids_out, B, W, g.ids, Tc, s);
     for (int t = 0; t < L.maxlen - 1; ++t) {
@@ -2026,12 +2006,8 @@ struct capgen_engine {
   // The loop of beam (end_id == nullptr: the reference's search, model.py:135-200) and of beam_nbest: leaves
   // the k * B hypotheses in g.seq, their scores in g.bprob and, for beam_nbest, g.bfin / g.blen.
   void beam_run(const void* feats, DType ft, const float* pos, int B, int N, int k, const int* end_id, hipStream_t s) {
-    ensure_acts(B, N, 2);
-    ensure_gen(k * B, N);
-    ensure_dtiles();
     const int R = k * B, Tc = L.maxlen, Tw = L.maxlen;
-    encode_only(feats, ft, pos, B, N, s);
-    build_dtiles(s);
+    begin_decode(feats, ft, pos, B, N, R, s);
     init_gen_ids(g.seq, R, Tw, g.ids, Tc, s);  // (Tw == Tc)
     // position 0: every beam holds <START>; top-k of beam 0's distribution (model.py:148-166)
     beam_kvrow(g.kvrow2, g.kvrow, Tc, -1, g.ids, B, R, s);  // [r][0] = r
@@ -2043,70 +2019,43 @@ struct capgen_engine {
       memset_async(g.bfin, sizeof(int32_t) * R, s);
       memset_async(g.blen, sizeof(int32_t) * R, s);
     }
-    // the END-aware step's state: read from bfin / blen, written to bfin2 / blen2, then swapped
-    auto ended = [&] { return BeamEnd{g.bfin, g.blen, g.bfin2, g.blen2, *end_id}; };
-    auto swap_ended = [&] {
-      std::swap(g.bfin, g.bfin2);
-      std::swap(g.blen, g.blen2);
-    };
-    auto fused = [&](int t, const float* prev, int kin, float* out_prob) {
-      if (end_id) {
-        beam_slab_step_ended(g.logits, g.dstats, prev, kin, B, L.V, k, out_prob, g.bsrc, g.btok, g.seq, g.seq2, Tw,
-                             g.ids, g.ids2, g.kvrow, g.kvrow2, Tc, t, ended(), s);
-        swap_ended();
-      } else {
-        beam_slab_step(g.logits, g.dstats, prev, kin, B, L.V, k, decode_logsm, out_prob, g.bsrc, g.btok, g.seq,
+    // The selection of position t over the k_in live beams per image with scores prev, and the reorder
+    // behind it.  The K/V cache is never copied: row r writes its position-t K/V at [l][r][t] and reads
+    // position j of its history from row kvrow[r][j] (the beam it descended from there); a reorder
+    // moves only the ids / sequences and this [R][Tc] table
+    auto select = [&](int t, const float* prev, int k_in) {
+      // the END-aware step's state: read from bfin / blen, written to bfin2 / blen2, then swapped
+      const BeamEnd ended = end_id ? BeamEnd{g.bfin, g.blen, g.bfin2, g.blen2, *end_id} : BeamEnd{};
+      if (fused_step && end_id)
+        beam_slab_step_ended(g.logits, g.dstats, prev, k_in, B, L.V, k, g.bprob2, g.bsrc, g.btok, g.seq, g.seq2, Tw,
+                             g.ids, g.ids2, g.kvrow, g.kvrow2, Tc, t, ended, s);
+      else if (fused_step)
+        beam_slab_step(g.logits, g.dstats, prev, k_in, B, L.V, k, decode_logsm, g.bprob2, g.bsrc, g.btok, g.seq,
                        g.seq2, Tw, g.ids, g.ids2, g.kvrow, g.kvrow2, Tc, t, s);
-      }
-      std::swap(g.seq, g.seq2);
-      std::swap(g.ids, g.ids2);
-      std::swap(g.kvrow, g.kvrow2);
-    };
-    // (beam_nbest off the fused path: the full-row kernels, which read the f32 logits of either dtype)
-    auto full_row_ended = [&](const float* prev, int kin, float* out_prob) {
-      beam_step_topk_ended(g.logits, prev, kin, B, L.V, k, g.cand_v, g.cand_i, out_prob, g.bsrc, g.btok, ended(), s);
-      swap_ended();
-    };
-    if (fused_step)  // (beam 0's finalists only: every source is beam 0 at t = 0)
-      fused(0, nullptr, 1, g.bprob);
-    else if (end_id)
-      full_row_ended(nullptr, 1, g.bprob);
-    else if (slab_decode())
-      beam_step_topk_slab(g.logits, g.dstats, nullptr, 1, B, L.V, k, decode_logsm, g.cand_v, g.cand_i, g.bprob, g.bsrc,
-                          g.btok, s);
-    else
-      beam_step_topk(g.logits, nullptr, 1, B, L.V, k, decode_logsm, g.cand_v, g.cand_i, g.bprob, g.bsrc, g.btok, s);
-    if (!fused_step) CAPGEN_HIP(hipMemsetAsync(g.bsrc, 0, sizeof(int32_t) * R, s));  // all beams descend from beam 0
-    // The K/V cache is never copied: row r writes its position-t K/V at [l][r][t] and reads
-    // position j of its history from row kvrow[r][j] (the beam it descended from there); a
-    // reorder moves only the ids / sequences and this [R][Tc] table
-    auto reorder = [&](int t) {
-      // seq/ids rows follow their source beam, then column t+1 = chosen token
-      beam_gather(g.seq, g.seq2, Tw, g.bsrc, B, R, g.btok, t + 1, s);
-      beam_gather(g.ids, g.ids2, Tc, g.bsrc, B, R, g.btok, t + 1, s);
-      beam_kvrow(g.kvrow, g.kvrow2, Tc, t, g.bsrc, B, R, s);
-      std::swap(g.seq, g.seq2);
-      std::swap(g.ids, g.ids2);
-      std::swap(g.kvrow, g.kvrow2);
-    };
-    if (!fused_step) reorder(0);
-    for (int t = 1; t < Tw - 1; ++t) {
-      dec_step(R, B, N, t, g.cache, g.ids, false, s, g.kvrow);
-      if (fused_step) {
-        fused(t, g.bprob, k, g.bprob2);
-        std::swap(g.bprob, g.bprob2);
-        continue;
-      }
-      if (end_id)
-        full_row_ended(g.bprob, k, g.bprob2);
+      else if (end_id)  // (off the fused path: the full-row kernel, which reads the f32 logits of either dtype)
+        beam_step_topk_ended(g.logits, prev, k_in, B, L.V, k, g.cand_v, g.cand_i, g.bprob2, g.bsrc, g.btok, ended, s);
       else if (slab_decode())
-        beam_step_topk_slab(g.logits, g.dstats, g.bprob, k, B, L.V, k, decode_logsm, g.cand_v, g.cand_i, g.bprob2,
+        beam_step_topk_slab(g.logits, g.dstats, prev, k_in, B, L.V, k, decode_logsm, g.cand_v, g.cand_i, g.bprob2,
                             g.bsrc, g.btok, s);
       else
-        beam_step_topk(g.logits, g.bprob, k, B, L.V, k, decode_logsm, g.cand_v, g.cand_i, g.bprob2, g.bsrc, g.btok,
-                       s);
+        beam_step_topk(g.logits, prev, k_in, B, L.V, k, decode_logsm, g.cand_v, g.cand_i, g.bprob2, g.bsrc, g.btok, s);
       std::swap(g.bprob, g.bprob2);
-      reorder(t);
+      if (end_id) std::swap(g.bfin, g.bfin2), std::swap(g.blen, g.blen2);
+      if (!fused_step) {
+        if (t == 0) memset_async(g.bsrc, sizeof(int32_t) * R, s);  // all beams descend from beam 0
+        // seq/ids rows follow their source beam, then column t+1 = chosen token
+        beam_gather(g.seq, g.seq2, Tw, g.bsrc, B, R, g.btok, t + 1, s);
+        beam_gather(g.ids, g.ids2, Tc, g.bsrc, B, R, g.btok, t + 1, s);
+        beam_kvrow(g.kvrow, g.kvrow2, Tc, t, g.bsrc, B, R, s);
+      }
+      std::swap(g.seq, g.seq2);
+      std::swap(g.ids, g.ids2);
+      std::swap(g.kvrow, g.kvrow2);
+    };
+    select(0, nullptr, 1);  // (beam 0's finalists only: every source is beam 0 at t = 0)
+    for (int t = 1; t < Tw - 1; ++t) {
+      dec_step(R, B, N, t, g.cache, g.ids, false, s, g.kvrow);
+      select(t, g.bprob, k);
     }
   }
 
@@ -2130,11 +2079,7 @@ struct capgen_engine {
     const float inv_tau = 1.f / temperature;
     require(inv_tau > 0.f && inv_tau < INFINITY, "sample: temperature out of range");
     const int R = n * B, Tc = L.maxlen, W = L.maxlen + 1;
-    ensure_acts(B, N, 2);
-    ensure_gen(R, N);
-    ensure_dtiles();
-    encode_only(feats, ft, pos, B, N, s);
-    build_dtiles(s);
+    begin_decode(feats, ft, pos, B, N, R, s);
     init_gen_ids(ids_out, R, W, g.ids, Tc, s);
     for (int t = 0; t < L.maxlen - 1; ++t) {
       dec_step(R, B, N, t, g.cache, g.ids, false, s);
@@ -2205,6 +2150,19 @@ DType dt(int x) {
 void set_device(capgen_t* h) {
   require(h != nullptr, "null engine handle");
   CAPGEN_HIP(hipSetDevice(h->device));
+}
+
+// a decode entry point: body() enqueued on the engine's stream between the caller's stream's events
+// (an exception leaves the engine's stream unjoined, as it may have left it half-enqueued)
+template <class F>
+int decode_call(capgen_t* h, void* stream, F&& body) {
+  return guarded([&] {
+    set_device(h);
+    hipStream_t cs = (hipStream_t)stream;
+    h->enter(cs);
+    body();
+    h->leave(cs);
+  });
 }
 
 void pe_table(const Layout& L, std::vector<float>& out) {
@@ -2543,59 +2501,34 @@ int capgen_copy_logits(capgen_t* h, float* dst, int64_t n, void* stream) {
 
 int capgen_greedy(capgen_t* h, const void* feats, int ft, const float* pos, int B, int N, int64_t* ids_out,
                   float* attn_out, void* stream) {
-  return guarded([&] {
-    set_device(h);
-    hipStream_t cs = (hipStream_t)stream;
-    h->enter(cs);
-    h->greedy(feats, dt(ft), pos, B, N, ids_out, attn_out, h->es);
-    h->leave(cs);
-  });
+  return decode_call(h, stream, [&] { h->greedy(feats, dt(ft), pos, B, N, ids_out, attn_out, h->es); });
 }
 
 int capgen_beam(capgen_t* h, const void* feats, int ft, const float* pos, int B, int N, int k, int64_t* ids_out,
                 void* stream) {
-  return guarded([&] {
-    set_device(h);
-    hipStream_t cs = (hipStream_t)stream;
-    h->enter(cs);
-    h->beam(feats, dt(ft), pos, B, N, k, ids_out, h->es);
-    h->leave(cs);
-  });
+  return decode_call(h, stream, [&] { h->beam(feats, dt(ft), pos, B, N, k, ids_out, h->es); });
 }
 
 int capgen_beam_nbest(capgen_t* h, const void* feats, int ft, const float* pos, int B, int N, int k, int end_id,
                       float length_penalty, int n_best, int64_t* ids_out, float* score_out, float* logp_out,
                       int32_t* len_out, void* stream) {
-  return guarded([&] {
-    set_device(h);
-    hipStream_t cs = (hipStream_t)stream;
-    h->enter(cs);
+  return decode_call(h, stream, [&] {
     h->beam_nbest(feats, dt(ft), pos, B, N, k, end_id, length_penalty, n_best, ids_out, score_out, logp_out, len_out,
                   h->es);
-    h->leave(cs);
   });
 }
 
 int capgen_sample(capgen_t* h, const void* feats, int ft, const float* pos, int B, int N, int n_samples,
                   float temperature, int top_k, uint64_t sd, int64_t* ids_out, float* logp_out, void* stream) {
-  return guarded([&] {
-    set_device(h);
-    hipStream_t cs = (hipStream_t)stream;
-    h->enter(cs);
-    h->sample(feats, dt(ft), pos, B, N, n_samples, temperature, top_k, 1.f, sd, ids_out, logp_out, h->es);
-    h->leave(cs);
-  });
+  return capgen_sample_nucleus(h, feats, ft, pos, B, N, n_samples, temperature, top_k, 1.f, sd, ids_out, logp_out,
+                               stream);
 }
 
 int capgen_sample_nucleus(capgen_t* h, const void* feats, int ft, const float* pos, int B, int N, int n_samples,
                           float temperature, int top_k, float top_p, uint64_t sd, int64_t* ids_out, float* logp_out,
                           void* stream) {
-  return guarded([&] {
-    set_device(h);
-    hipStream_t cs = (hipStream_t)stream;
-    h->enter(cs);
+  return decode_call(h, stream, [&] {
     h->sample(feats, dt(ft), pos, B, N, n_samples, temperature, top_k, top_p, sd, ids_out, logp_out, h->es);
-    h->leave(cs);
   });
 }
 
