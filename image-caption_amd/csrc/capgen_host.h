@@ -25,7 +25,7 @@ inline void require(bool ok, const std::string& what) {
 enum class Knob : int {
   FusedCe, GroupDw, FusedQkv, FusedAttnBwd, ColsumSide, DecodeCrossMfma, SlabDecode, DecodeGroupLds, AttnWave,
   CeVec8, BregDecode, DecodeLnFold, FusedBeamStep, OverlapFront, OverlapDec0, StripeClear, BucketBlocks, Zero, FwdGraph, Streams,
-  EventFence, DeferLoss, FrontJoin, ClipAdamGrid, Autotune, AutotuneLog,
+  EventFence, DeferLoss, FrontJoin, ClipAdamGrid, Autotune, AutotuneLog, DwGrid,
   Skip, DebugDropJoin, SplitkProto, AllowPartialLines, DwVariant, HostTiming,  // debug build only
   Count
 };

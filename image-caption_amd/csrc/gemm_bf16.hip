@@ -204,7 +204,7 @@ int g_variant = 0;  // experiment selector (capgen_debug_gemm_variant); 0 = tune
 // Tile / wave-grid / pipeline-depth variants.  Every variant accumulates the same K tiles
 // in the same order with the same MFMA sequence, so results are bit-identical across
 // variants: the choice is a pure speed decision (made per shape by the autotuner).
-constexpr int NVARIANTS = 30;
+constexpr int NVARIANTS = 36;
 const char* kVariantName[NVARIANTS + 1] = {"auto",        "128x128w4s3", "128x128w8s2",  "128x128w4s2",
                                            "128x64w4s2",  "64x128w4s2",  "64x64w4s2",    "64x64w4s3",
                                            "128x64w8s2",  "256x128w16s2", "128x128w16s2", "256x64w8s2",
@@ -213,15 +213,21 @@ const char* kVariantName[NVARIANTS + 1] = {"auto",        "128x128w4s3", "128x12
                                            "64x64w8s2",   "32x64w4s3",   "64x32w4s3",
                                            // k-group variants (TileCfg KG): 'k2' = 2 k-groups of the waves named
                                            "64x64w4k2s2", "64x64w4k2s3", "32x64w4k2s3", "64x64w4k4s2",
-                                           "32x64w4k4s2", "128x64w4k2s2", "64x128w4k2s2", "32x64w4k2s2"};
+                                           "32x64w4k4s2", "128x64w4k2s2", "64x128w4k2s2", "32x64w4k2s2",
+                                           // deep rings for the 8- and 16-wave tiles (one workgroup per CU in the
+                                           // capped weight-gradient grid: the ring is all that keeps DMA in flight)
+                                           "128x128w16s3", "128x128w16s4", "128x128w8s3", "128x64w8s3",
+                                           "128x64w8s4",  "256x128w16s3"};
 
 // output tile width (columns) of each variant
 constexpr int kVariantBN[NVARIANTS + 1] = {0,  128, 128, 128, 64, 128, 64, 64, 64, 128, 128, 64,
                                            64, 64,  64,  128, 128, 64, 32, 32, 64, 64,  32,
-                                           64, 64,  64,  64,  64,  64, 128, 64};
+                                           64, 64,  64,  64,  64,  64, 128, 64,
+                                           128, 128, 128, 64, 64, 128};
 // k-groups of each variant (grid split-K only for KG == 1)
 constexpr int kVariantKG[NVARIANTS + 1] = {0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
-                                           1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 4, 4, 2, 2, 2};
+                                           1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 4, 4, 2, 2, 2,
+                                           1, 1, 1, 1, 1, 1};
 
 // A tile whose output row segment is narrower than a 128-B cache line shares lines of C with
 // its neighbour tile, which another workgroup -- possibly on another XCD -- writes in the same
@@ -269,6 +275,12 @@ static void launch_variant(int v, const GemmArgs& g, hipStream_t s, int sk = 1) 
     case 28: return launch_cfg<TO, TA, TB, 128, 64, 2, 2, 2, 2>(g, s, sk);
     case 29: return launch_cfg<TO, TA, TB, 64, 128, 2, 2, 2, 2>(g, s, sk);
     case 30: return launch_cfg<TO, TA, TB, 32, 64, 2, 2, 2, 2>(g, s, sk);
+    case 31: return launch_cfg<TO, TA, TB, 128, 128, 4, 4, 3>(g, s, sk);
+    case 32: return launch_cfg<TO, TA, TB, 128, 128, 4, 4, 4>(g, s, sk);
+    case 33: return launch_cfg<TO, TA, TB, 128, 128, 2, 4, 3>(g, s, sk);
+    case 34: return launch_cfg<TO, TA, TB, 128, 64, 4, 2, 3>(g, s, sk);
+    case 35: return launch_cfg<TO, TA, TB, 128, 64, 4, 2, 4>(g, s, sk);
+    case 36: return launch_cfg<TO, TA, TB, 256, 128, 4, 4, 3>(g, s, sk);
     default: throw Error("gemm: unknown variant");
   }
 }
@@ -489,8 +501,9 @@ static void launch_group_cfg(const GemmArgs* ps, int n, hipStream_t s) {
   // the grouped (weight-gradient) grid is capped at one workgroup per CU, each looping over its
   // tiles: the side-stream dW work then leaves room on every CU for the critical stream's
   // latency-bound kernels (step 3.44-3.47 vs 3.54 ms uncapped; 64 workgroups: 3.75 ms, the dW
-  // work becomes critical; round 4 re-sweep: 256 vs 192 / 320 / 128, tools/r04_dwgrid.sh).
+  // work becomes critical; round 4 re-sweep: 256 vs 192 / 320 / 128; CAPGEN_DW_GRID, tools/dw_grid_sweep.sh).
   static const int cap = [] {
+    if (const int k = knob(Knob::DwGrid)) return std::max(8, k / 8 * 8);  // (the sweep: tools/dw_grid_sweep.sh)
     int n = 0, dev = 0;
     CAPGEN_HIP(hipGetDevice(&dev));
     CAPGEN_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
@@ -504,7 +517,7 @@ static void launch_group_cfg(const GemmArgs* ps, int n, hipStream_t s) {
 }
 
 // the variants worth a grouped launch (many tiles already: no split-K)
-constexpr int kGroupVariants[] = {6, 20, 17, 18, 19, 4, 8, 1, 3, 10};
+constexpr int kGroupVariants[] = {6, 20, 17, 18, 19, 4, 8, 1, 3, 10, 31, 32, 33, 34, 35, 36};
 
 template <typename TO, bool TA, bool TB>
 static void launch_group_variant(int v, const GemmArgs* ps, int n, hipStream_t s) {
@@ -519,6 +532,12 @@ static void launch_group_variant(int v, const GemmArgs* ps, int n, hipStream_t s
     case 18: return launch_group_cfg<TO, TA, TB, 64, 32, 2, 2, 2>(ps, n, s);
     case 19: return launch_group_cfg<TO, TA, TB, 32, 32, 2, 2, 2>(ps, n, s);
     case 20: return launch_group_cfg<TO, TA, TB, 64, 64, 4, 2, 2>(ps, n, s);
+    case 31: return launch_group_cfg<TO, TA, TB, 128, 128, 4, 4, 3>(ps, n, s);
+    case 32: return launch_group_cfg<TO, TA, TB, 128, 128, 4, 4, 4>(ps, n, s);
+    case 33: return launch_group_cfg<TO, TA, TB, 128, 128, 2, 4, 3>(ps, n, s);
+    case 34: return launch_group_cfg<TO, TA, TB, 128, 64, 4, 2, 3>(ps, n, s);
+    case 35: return launch_group_cfg<TO, TA, TB, 128, 64, 4, 2, 4>(ps, n, s);
+    case 36: return launch_group_cfg<TO, TA, TB, 256, 128, 4, 4, 3>(ps, n, s);
     default: throw Error("gemm_grouped: unknown variant");
   }
 }
@@ -556,6 +575,9 @@ static void launch_group(const GemmArgs* ps, int n, hipStream_t s) {
         for (int cand : kGroupVariants) {
           if (!whole_lines<TO>(cand)) continue;
           const float ms = tune_time([&] { launch_group_variant<TO, TA, TB>(cand, t.data(), n, s); }, s, e0, e1);
+          if (knob(Knob::AutotuneLog) > 1)  // every candidate, for building in-step A/B tables
+            std::fprintf(stderr, "[capgen gemm]   group of %d (K=%d): %s %.2f us\n", n, ps[0].K, kVariantName[cand],
+                         ms * 1e3f / 3);
           if (ms < best) best = ms, v = cand;
         }
         CAPGEN_HIP(hipEventDestroy(e0));

@@ -275,6 +275,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int mt, int nt, int
   // k-loop unrolled by STAGES: tile kb + s lives in stage s, so every LDS offset is a constant
   // (ds_read immediate offsets, a scalar M0 per DMA piece: no address VALU in the loop)
   static_assert((STAGES - 2) * LPT <= 63, "vmcnt range");
+  static_assert(Cfg::SMEM <= 160 * 1024, "the ring must fit a CU's 160 KB of LDS");
   // (every k-group runs per_g trips -- the barriers stay uniform -- and works on its own nk)
   for (int kb = 0; kb < per_g; kb += STAGES) {
 #pragma unroll

@@ -56,7 +56,8 @@ constexpr KnobDef kDefs[] = {
     {Knob::FrontJoin, "FRONT_JOIN", 99, false},       // forward joins the decoder front before encoder block N (> Le: before the decoder)
     {Knob::ClipAdamGrid, "CLIP_ADAM_GRID", 2048, false},  // Adam workgroups of the clipped step's deferred buckets (0: the bucket's own cap)
     {Knob::Autotune, "AUTOTUNE", 1, false},           // time GEMM shapes the tune table lacks
-    {Knob::AutotuneLog, "AUTOTUNE_LOG", 0, false},    // print tuning decisions
+    {Knob::AutotuneLog, "AUTOTUNE_LOG", 0, false},    // print tuning decisions (2: every grouped candidate)
+    {Knob::DwGrid, "DW_GRID", 0, false},              // grouped (weight-gradient) grid cap in workgroups (0: one per CU)
     // debug build only
     {Knob::Skip, "SKIP", 0, true},                             // kernel classes to skip (marginal-cost probes)
     {Knob::DebugDropJoin, "DEBUG_DROP_JOIN", 0, true},         // drop the side-stream join (checker self-test)
