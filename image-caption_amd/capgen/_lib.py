@@ -62,6 +62,23 @@ class capgen_attn_geom(C.Structure):
     ]
 
 
+class capgen_decode_constraints(C.Structure):
+    """capgen_decode_constraints (include/capgen.h); banned is a host array the call copies"""
+    _fields_ = [("no_repeat_ngram", C.c_int32), ("min_length", C.c_int32), ("end_id", C.c_int32),
+                ("repetition_penalty", C.c_float), ("banned", C.POINTER(C.c_int32)), ("n_banned", C.c_int32)]
+
+
+def decode_constraints(no_repeat_ngram=0, min_length=0, end_id=-1, repetition_penalty=1.0, banned=()):
+    """The struct for capgen_set_decode_constraints / capgen_debug_constrain_logits (it keeps its list alive)"""
+    ids = [int(w) for w in banned]
+    c = capgen_decode_constraints(int(no_repeat_ngram), int(min_length), int(end_id), float(repetition_penalty),
+                                  None, len(ids))
+    if ids:
+        c._banned = (C.c_int32 * len(ids))(*ids)
+        c.banned = C.cast(c._banned, C.POINTER(C.c_int32))
+    return c
+
+
 _SIGS = {
     "capgen_last_error": (C.c_char_p, []),
     "capgen_abi_version": (C.c_int, []),
@@ -99,6 +116,9 @@ _SIGS = {
                                 _P]),
     "capgen_sample_nucleus": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
                                         C.c_uint64, _P, _P, _P]),
+    "capgen_set_decode_constraints": (C.c_int, [_P, C.POINTER(capgen_decode_constraints)]),
+    "capgen_debug_constrain_logits": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int64, C.c_int,
+                                                C.POINTER(capgen_decode_constraints), _P]),
     "capgen_set_rng_seed": (C.c_int, [_P, C.c_uint64]),
     "capgen_debug_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int,
                                     _P, C.c_int64, C.c_int, C.c_int, _P, C.c_float, C.c_int, C.c_int, _P]),

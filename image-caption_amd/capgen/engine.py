@@ -358,6 +358,20 @@ class Engine:
                                               _ptr(length), _stream(self.device)))
         return ids.view(n, B, T), score.view(n, B), logp.view(n, B), length.view(n, B)
 
+    def set_decode_constraints(self, no_repeat_ngram=0, min_length=0, end_id=-1, repetition_penalty=1.0, banned=()):
+        """What beam_nbest and sample may not say, from now on (capgen_set_decode_constraints; greedy and beam
+        are never constrained): no n-gram twice (no_repeat_ngram = n, 0: off), no end_id before min_length
+        tokens (0: off), every emitted word's logit divided (positive) or multiplied (negative) by
+        repetition_penalty (1.0: off), and the word ids in banned never.  A blocked word has probability
+        exactly 0 and every score, mass and logp is taken over what is left.  Called with no arguments:
+        everything off (the default).  One more launch per decode step while anything is on."""
+        banned = tuple(banned)
+        if not (no_repeat_ngram or min_length or banned) and float(repetition_penalty) == 1.0:
+            _lib.check(self.lib.capgen_set_decode_constraints(self.h, None))
+            return
+        c = _lib.decode_constraints(no_repeat_ngram, min_length, end_id, repetition_penalty, banned)
+        _lib.check(self.lib.capgen_set_decode_constraints(self.h, C.byref(c)))
+
     def sample(self, feats, pos, n_samples=1, temperature=1.0, top_k=0, seed=0, want_logp=True, top_p=1.0):
         """n_samples captions per image drawn from softmax(logits / temperature) over the top_k largest
         logits (0: the whole vocabulary), KV-cached, one encoder pass (capgen_sample_nucleus).  top_p in

@@ -8,6 +8,8 @@ models.py:120-122).
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 import torch
 
@@ -29,6 +31,7 @@ class MODEL_init:
                 raise ValueError("capgen: pass word_to_idx or word_to_idx_path (models.py:22)")
             word_to_idx = load_word_to_idx(word_to_idx_path)
         self.num_vocab = len(word_to_idx)
+        self.word_to_idx = dict(word_to_idx)
         self.idx_to_word = {i: w for w, i in word_to_idx.items()}
         self.end_idx = word_to_idx.get("<END>")
         self.model = None
@@ -52,28 +55,61 @@ class MODEL_init:
         assert isinstance(beam_size, int)
         assert beam_size > 1 or beam_size in [None, 1]
 
-    def beam_captions(self, object_features, position_features, beam_size, length_penalty=0.0, n_best=1):
+    @contextlib.contextmanager
+    def _constrained(self, no_repeat_ngram, min_length, repetition_penalty, banned_words):
+        """The engine's decode constraints for one generation call: set on entry where any is asked for and
+        switched off again on the way out, whatever happened, so that nothing leaks into a later call or a
+        trainer's roll-outs.  banned_words are words of the vocabulary; <END> comes from it too."""
+        banned = []
+        for w in banned_words:
+            if w not in self.word_to_idx:
+                raise ValueError(f"capgen: banned word {w!r} is not in the vocabulary")
+            banned.append(int(self.word_to_idx[w]))
+        if min_length and self.end_idx is None:
+            raise ValueError("capgen: min_length needs <END> in the vocabulary")
+        on = bool(no_repeat_ngram or min_length or banned) or float(repetition_penalty) != 1.0
+        engine = self.model.engine
+        try:
+            if on:
+                engine.set_decode_constraints(no_repeat_ngram=no_repeat_ngram, min_length=min_length,
+                                              end_id=-1 if self.end_idx is None else int(self.end_idx),
+                                              repetition_penalty=repetition_penalty, banned=banned)
+            yield
+        finally:
+            if on:
+                engine.set_decode_constraints()
+
+    def beam_captions(self, object_features, position_features, beam_size, length_penalty=0.0, n_best=1,
+                      no_repeat_ngram=0, min_length=0, repetition_penalty=1.0, banned_words=()):
         """The n_best captions per image of a beam search that stops at <END> (generate_caption keeps the
         reference's search, which does not): (captions, score) -- n_best lists of B strings, best first, and
         their scores [n_best, B] (f32, on the model's device): the caption's log-probability through <END>
         divided by its length ** length_penalty (0.0: the log-probability itself).  A vocabulary without
-        <END> searches to max_length."""
+        <END> searches to max_length.  Constraints, for this call only (Engine.set_decode_constraints): no
+        n-gram of no_repeat_ngram words twice, no <END> before min_length tokens, the logits of the words
+        already said scaled down by repetition_penalty, and banned_words (e.g. "<NULL>", "<START>", "<UNK>")
+        never; the scores are log-probabilities under the constrained distribution."""
         end = -1 if self.end_idx is None else int(self.end_idx)
-        ids, score, _, _ = self.model.beam_search_nbest(object_features=object_features,
-                                                        position_features=position_features, beam_size=beam_size,
-                                                        end_id=end, length_penalty=length_penalty, n_best=n_best)
+        with self._constrained(no_repeat_ngram, min_length, repetition_penalty, banned_words):
+            ids, score, _, _ = self.model.beam_search_nbest(object_features=object_features,
+                                                            position_features=position_features, beam_size=beam_size,
+                                                            end_id=end, length_penalty=length_penalty, n_best=n_best)
         host = ids.cpu().numpy()
         return [self.decode_captions(host[j]) for j in range(host.shape[0])], score
 
     def sample_captions(self, object_features, position_features, n_samples=1, temperature=1.0, top_k=0, seed=None,
-                        top_p=1.0):
+                        top_p=1.0, no_repeat_ngram=0, min_length=0, repetition_penalty=1.0, banned_words=()):
         """n_samples captions per image drawn from the model's distribution (temperature / top-k /
         nucleus top_p sampling): (captions, logprob) -- n lists of B strings and each caption's log-probability
-        [n, B] (f32, on the model's device: the sum of its token log-probabilities through <END>)."""
-        ids, logp = self.model.sample_caption_vector(object_features=object_features,
-                                                     position_features=position_features, n_samples=n_samples,
-                                                     temperature=temperature, top_k=top_k, seed=seed,
-                                                     top_p=top_p)
+        [n, B] (f32, on the model's device: the sum of its token log-probabilities through <END>).
+        no_repeat_ngram, min_length, repetition_penalty and banned_words constrain this call as they do
+        beam_captions; the log-probabilities are then those of the constrained distribution, which is why
+        the self-critical trainers' roll-outs never use them (they would be off-policy)."""
+        with self._constrained(no_repeat_ngram, min_length, repetition_penalty, banned_words):
+            ids, logp = self.model.sample_caption_vector(object_features=object_features,
+                                                         position_features=position_features, n_samples=n_samples,
+                                                         temperature=temperature, top_k=top_k, seed=seed,
+                                                         top_p=top_p)
         host = ids.cpu().numpy()
         end = -1 if self.end_idx is None else self.end_idx  # (no <END> in the vocabulary: every token counts)
         logprob = sequence_logprob(ids[..., 1:logp.shape[-1] + 1], logp, end)

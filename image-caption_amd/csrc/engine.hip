@@ -893,6 +893,9 @@ struct capgen_engine {
   // decode scoring: false = Softmax, probabilities accumulated over beams (Transformer,
   // model.py:124-128,183); true = LogSoftmax, log-probabilities (PolicyNetwork, model_RL.py:72,182)
   bool decode_logsm = false;
+  // decode constraints of beam_nbest and sample (select.hip; capgen_set_decode_constraints): off by default
+  DecodeConstraints dc;
+  int32_t* dc_banned = nullptr;  // the device copy of the banned list dc.banned points to (1024 entries)
 
   // ------------------------------------------------------------------------------------
   // one EncoderBlock (modules.py:146-157) over B sequences of N rows: X -> Xout.  valid != null:
@@ -1999,6 +2002,8 @@ struct capgen_engine {
     require(N >= 1 && N <= 64, "beam_nbest: N must be in [1, 64]");
     require(B >= 1, "beam_nbest: need B >= 1");
     require(ids_out != nullptr, "beam_nbest: null ids_out");
+    require(dc.min_length == 0 || dc.end_id == end_id,
+            "beam_nbest: end_id differs from the end_id of the decode constraints' min_length");
     beam_run(feats, ft, pos, B, N, k, &end_id, s);
     beam_finish(g.seq, g.bprob, g.blen, k, B, L.maxlen, alpha, n_best, ids_out, score_out, logp_out, len_out, s);
   }
@@ -2012,6 +2017,9 @@ struct capgen_engine {
     // position 0: every beam holds <START>; top-k of beam 0's distribution (model.py:148-166)
     beam_kvrow(g.kvrow2, g.kvrow, Tc, -1, g.ids, B, R, s);  // [r][0] = r
     dec_step(R, B, N, 0, g.cache, g.ids, false, s);
+    // decode constraints edit the step's logits (and repair the slab stats) in front of beam_nbest's selection
+    const bool constrained = end_id && dc.on();
+    if (constrained) constrain_logits(g.logits, slab_decode() ? g.dstats : nullptr, R, L.V, g.ids, Tc, 0, dc, s);
     // bf16: the selection and the reorder of a step as one launch per image (beam_slab_step:
     // CAPGEN_FUSED_BEAM_STEP=0 restores the top-k, merge and three reorder launches)
     const bool fused_step = slab_decode() && fused_beam_step_on && k <= 16 && Tw == Tc;
@@ -2055,6 +2063,7 @@ struct capgen_engine {
     select(0, nullptr, 1);  // (beam 0's finalists only: every source is beam 0 at t = 0)
     for (int t = 1; t < Tw - 1; ++t) {
       dec_step(R, B, N, t, g.cache, g.ids, false, s, g.kvrow);
+      if (constrained) constrain_logits(g.logits, slab_decode() ? g.dstats : nullptr, R, L.V, g.ids, Tc, t, dc, s);
       select(t, g.bprob, k);
     }
   }
@@ -2083,6 +2092,7 @@ struct capgen_engine {
     init_gen_ids(ids_out, R, W, g.ids, Tc, s);
     for (int t = 0; t < L.maxlen - 1; ++t) {
       dec_step(R, B, N, t, g.cache, g.ids, false, s);
+      if (dc.on()) constrain_logits(g.logits, slab_decode() ? g.dstats : nullptr, R, L.V, g.ids, Tc, t, dc, s);
       if (top_p == 1.f)
         sample_softmax(g.logits, R, L.V, inv_tau, top_k, sd, kSampleSite0 + (uint32_t)t, ids_out, W, t + 1,
                        g.ids + t + 1, Tc, logp_out, Tc - 1, t, s);
@@ -2097,7 +2107,8 @@ struct capgen_engine {
     drop_graph();
     if (comm) ncclCommDestroy(comm);
     for (void* p : {(void*)params, (void*)grads, (void*)am, (void*)av, (void*)shadow, (void*)wtile, (void*)dtiles, (void*)emb_bf, (void*)pe, (void*)step,
-                    (void*)adam_scal, (void*)seed, (void*)scalars, (void*)gstripe, ws, gws, (void*)stamp_ring})
+                    (void*)adam_scal, (void*)seed, (void*)scalars, (void*)gstripe, ws, gws, (void*)stamp_ring,
+                    (void*)dc_banned})
       if (p) (void)hipFree(p);
     if (count_host) (void)hipHostFree(count_host);
     if (opt_host) (void)hipHostFree(opt_host);
@@ -2381,6 +2392,48 @@ int capgen_set_decode_log_softmax(capgen_t* h, int enable) {
   return guarded([&] {
     require(h != nullptr, "null engine handle");
     h->decode_logsm = enable != 0;
+  });
+}
+
+// The ranges of a capgen_decode_constraints for a vocabulary of V words and captions of T = max_length
+// (0: not known, the kernel hook) -> the launcher's form, its banned list still the caller's host array.
+static DecodeConstraints checked_constraints(const capgen_decode_constraints& c, int V, int T, const std::string& who) {
+  require(c.no_repeat_ngram >= 0 && (T == 0 || c.no_repeat_ngram < T),
+          who + ": no_repeat_ngram must be 0 or in [1, max_length)");
+  require(c.end_id >= -1 && c.end_id < V, who + ": end_id must be in [-1, num_vocab)");
+  require(c.min_length >= 0 && (T == 0 || c.min_length <= T - 1), who + ": min_length must be 0 or in [1, max_length - 1]");
+  require(c.min_length == 0 || c.end_id >= 0, who + ": min_length needs an end_id >= 0");
+  require(c.repetition_penalty > 0.f && c.repetition_penalty < INFINITY,
+          who + ": repetition_penalty must be finite and > 0");  // (false for a NaN)
+  require(c.n_banned >= 0 && c.n_banned <= 1024, who + ": n_banned must be in [0, 1024]");
+  require(c.n_banned == 0 || c.banned != nullptr, who + ": null banned list with n_banned > 0");
+  for (int i = 0; i < c.n_banned; ++i)
+    require(c.banned[i] >= 0 && c.banned[i] < V,
+            who + ": banned[" + std::to_string(i) + "] = " + std::to_string(c.banned[i]) + " must be in [0, num_vocab)");
+  DecodeConstraints d;
+  d.no_repeat_ngram = c.no_repeat_ngram, d.min_length = c.min_length, d.end_id = c.end_id;
+  d.repetition_penalty = c.repetition_penalty, d.banned = c.banned, d.n_banned = c.n_banned;
+  return d;
+}
+
+int capgen_set_decode_constraints(capgen_t* h, const capgen_decode_constraints* c) {
+  return guarded([&] {
+    require(h != nullptr, "null engine handle");
+    set_device(h);
+    if (!c) {
+      h->dc = DecodeConstraints{};
+      return;
+    }
+    DecodeConstraints d = checked_constraints(*c, h->L.V, h->L.maxlen, "set_decode_constraints");
+    require(h->L.V - d.n_banned - h->L.maxlen >= 16,
+            "set_decode_constraints: num_vocab - n_banned - max_length must be >= 16 (every row keeps 16 words)");
+    if (d.n_banned > 0) {
+      hz::host_sync(h->es);  // (an earlier decode may still read the former list)
+      if (!h->dc_banned) CAPGEN_HIP(hipMalloc(&h->dc_banned, sizeof(int32_t) * 1024));
+      CAPGEN_HIP(hipMemcpy(h->dc_banned, c->banned, sizeof(int32_t) * d.n_banned, hipMemcpyHostToDevice));
+    }
+    d.banned = d.n_banned > 0 ? h->dc_banned : nullptr;
+    h->dc = d;
   });
 }
 
@@ -3086,6 +3139,32 @@ int capgen_debug_beam_finish(const int64_t* seq, const float* logp, const int32_
   return guarded([&] {
     beam_finish(seq, logp, len, k, B, Tw, length_penalty, n_best, ids_out, score_out, logp_out, len_out,
                 (hipStream_t)stream);
+  });
+}
+
+int capgen_debug_constrain_logits(float* logits, void* stats, int R, int V, const int32_t* ids, int64_t ids_ld, int t,
+                                  const capgen_decode_constraints* c, void* stream) {
+  return guarded([&] {
+    require(c != nullptr, "debug_constrain_logits: null constraints");
+    require(V >= 1, "debug_constrain_logits: V >= 1");
+    DecodeConstraints d = checked_constraints(*c, V, 0, "debug_constrain_logits");
+    const hipStream_t s = (hipStream_t)stream;
+    int32_t* banned = nullptr;  // the list on the device for the one launch
+    if (d.n_banned > 0) {
+      CAPGEN_HIP(hipMalloc(&banned, sizeof(int32_t) * d.n_banned));
+      (void)hipMemcpy(banned, c->banned, sizeof(int32_t) * d.n_banned, hipMemcpyHostToDevice);
+    }
+    d.banned = banned;
+    try {
+      constrain_logits(logits, reinterpret_cast<float2*>(stats), R, V, ids, ids_ld, t, d, s);
+    } catch (...) {
+      if (banned) (void)hipFree(banned);
+      throw;
+    }
+    if (banned) {
+      (void)hipStreamSynchronize(s);
+      CAPGEN_HIP(hipFree(banned));
+    }
   });
 }
 

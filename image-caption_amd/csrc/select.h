@@ -69,6 +69,22 @@ void beam_slab_step_ended(const float* logits, const float2* stats, const float*
 void beam_finish(const int64_t* seq, const float* logp, const int32_t* len, int k, int B, int Tw, float alpha,
                  int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, hipStream_t s);
 
+// Decode constraints (beam_nbest and sample; definition: select.hip): what a row may not say next, from its
+// own token history.  banned is a DEVICE array here (the C ABI's struct carries a host one).
+struct DecodeConstraints {
+  int no_repeat_ngram = 0;         // 0: off
+  int min_length = 0;              // 0: off; needs end_id >= 0
+  int end_id = -1;
+  float repetition_penalty = 1.f;  // 1: off
+  const int32_t* banned = nullptr;
+  int n_banned = 0;
+  bool on() const { return no_repeat_ngram > 0 || min_length > 0 || repetition_penalty != 1.f || n_banned > 0; }
+};
+// edits logits [R][V] in place before the selection of position t (row r's history: ids[r * ids_ld + 1 .. t]);
+// stats (nullable): the rows' slab stats [R][ceil(V / 16)], rebuilt for every slab an edit touched
+void constrain_logits(float* logits, float2* stats, int R, int V, const int32_t* ids, int64_t ids_ld, int t,
+                      const DecodeConstraints& c, hipStream_t s);
+
 // the generation loops' bookkeeping
 // out [rows][width] (int64) and ids [rows][tcap] (int32): column 0 = <START> (1), the rest 0
 void init_gen_ids(int64_t* out, int rows, int width, int32_t* ids, int tcap, hipStream_t s);

@@ -1,8 +1,8 @@
 // capgen — decode selection kernels for gfx950: what turns a decode step's logits into tokens.
 //
 // Greedy argmax, the beam step's per-row top-k and per-image merge, temperature / top-k / nucleus
-// sampling by Gumbel-max, the bf16 path's selection from the classifier's slab stats, and the beam
-// bookkeeping of the generation loops.  Every selection orders candidates by (value descending, index
+// sampling by Gumbel-max, the bf16 path's selection from the classifier's slab stats, the decode constraints
+// that edit a step's logits in front of a selection, and the beam bookkeeping of the generation loops.  Every selection orders candidates by (value descending, index
 // ascending).  The pieces the kernels are built from -- the row in registers, the sorted per-thread
 // lists and the wave rounds over them, the block winner and the block reductions -- are in select_dev.h.
 #include <algorithm>
@@ -846,6 +846,130 @@ void beam_step_topk_slab(const float* logits, const float2* stats, const float* 
                                                                              cand_v, cand_i);
   });
   beam_merge_kernel<<<B, 64, 0, s>>>(cand_v, cand_i, k_in, B, V, k, out_prob, out_src, out_tok);
+  CAPGEN_HIP(hipGetLastError());
+}
+
+// ---- decode constraints: repetition penalty, banned words, minimum length, no-repeat n-grams ----
+// One launch between a decode step and its selection (beam_nbest and sample; greedy and beam are the
+// reference's decoders and are never constrained).  The step at position t predicts column t + 1.  Row r's
+// emitted tokens are e = ids[r][1 .. t]; <START> in column 0 is not counted.  From the classifier's logits z
+// the constrained logits are built in this order:
+// 1. Repetition penalty theta (1 = off).  For each distinct word w in e: z[w] <- z[w] / theta if z[w] > 0,
+//    else z[w] * theta (one f32 division or product).  Once per word, however often the word occurred.
+// 2. Banned words.  z[w] <- -inf for every w in the list.
+// 3. Minimum length m (0 = off).  z[end_id] <- -inf while t + 1 < m.  An <END> emitted at step t gives
+//    len = t + 1, as beam_nbest counts it.
+// 4. No-repeat n-gram n (0 = off), when t >= n - 1.  For every a with e[a .. a+n-2] equal to e[t-n+2 .. t],
+//    z[e[a+n-1]] <- -inf (a + n - 1 <= t).  With n = 1 every emitted word is blocked.
+// - "Blocked" is a logit of -inf, and a slab with nothing left has the stats {-inf, 0}.  Every selection kernel
+//   above takes both as absent: exp(-inf - M) and __expf(-inf - M) are 0 for the finite row maximum M, so a
+//   blocked word adds nothing to an exp-sum or to a nucleus mass and has probability exactly 0; its score
+//   (-inf - M) - lse, its Gumbel score -inf + g and its nucleus key (below every finite logit's) are -inf or
+//   last, and topk_insert / wave_best put a -inf candidate behind every finite one.  So a blocked word is
+//   selected only where a row has fewer finite words than the selection takes; the engine keeps at least 16
+//   (num_vocab - n_banned - max_length >= 16, the most any selection takes from a row).
+// - Softmax, log-softmax, top-k, nucleus mass and logp are all taken over what is left: logp_out stays the
+//   log-probability under the distribution the token was drawn from.
+// - Finished beam rows are edited like any other row: the END-aware step never reads their logits.  In
+//   sample <END> stays an ordinary word, so blocking goes on after it.
+// - A history entry outside [0, V) names no column and is skipped.
+// The kernel: one wave per row, the lanes striding over the history positions and the banned list (either
+// may be longer than 64), in three phases: (1) the penalty's read-modify-writes, on distinct columns since
+// only a word's first occurrence applies it; (2) the -inf stores, idempotent, so a word both penalised and
+// blocked ends blocked; (3) with stats, {max, sum __expf(v - max)} of every touched slab from its (up to 16,
+// the last slab of a row fewer) stored logits, summed in the classifier epilogue's order; two lanes repairing
+// one slab write the same value.  Between the phases the row's stores must be visible to the other lanes'
+// loads: every lane waits for its own stores (vmcnt counts stores on gfx9), then the workgroup barrier; the
+// waves of a workgroup share one CU and its write-through L1, so no cache invalidate is needed.
+__device__ __forceinline__ void workgroup_stores_visible() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
+// pen(w) for the first occurrence of every word in e[1 .. t], blk(w) for every blocked word (some twice)
+template <class Pen, class Blk>
+__device__ __forceinline__ void constrain_visit(const int32_t* __restrict__ e, int V, int t,
+                                                const DecodeConstraints& c, int lane, Pen&& pen, Blk&& blk) {
+  auto word = [&](int w) { return (unsigned)w < (unsigned)V; };
+  if (c.repetition_penalty != 1.f)
+    for (int p = 1 + lane; p <= t; p += 64) {
+      const int w = e[p];
+      bool first = word(w);
+      for (int q = 1; q < p && first; ++q) first = e[q] != w;
+      if (first) pen(w);
+    }
+  for (int i = lane; i < c.n_banned; i += 64) {
+    const int w = c.banned[i];
+    if (word(w)) blk(w);
+  }
+  if (lane == 0 && c.min_length > 0 && t + 1 < c.min_length && word(c.end_id)) blk(c.end_id);
+  const int n = c.no_repeat_ngram;
+  if (n > 0 && t >= n - 1)
+    for (int a = 1 + lane; a + n - 1 <= t; a += 64) {
+      bool match = true;
+      for (int i = 0; i < n - 1 && match; ++i) match = e[a + i] == e[t - n + 2 + i];
+      const int w = e[a + n - 1];
+      if (match && word(w)) blk(w);
+    }
+}
+
+__global__ void __launch_bounds__(64) constrain_logits_kernel(float* logits, float2* stats, int V, const int32_t* ids,
+                                                              int64_t ids_ld, int t, DecodeConstraints c) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  float* x = logits + (int64_t)r * V;
+  const int32_t* e = ids + (int64_t)r * ids_ld;
+  const float theta = c.repetition_penalty;
+  auto nothing = [](int) {};
+  constrain_visit(
+      e, V, t, c, lane,
+      [&](int w) {
+        const float z = x[w];
+        x[w] = z > 0.f ? __fdiv_rn(z, theta) : __fmul_rn(z, theta);
+      },
+      nothing);
+  workgroup_stores_visible();
+  constrain_visit(e, V, t, c, lane, nothing, [&](int w) { x[w] = -INFINITY; });
+  if (!stats) return;  // (the whole workgroup)
+  workgroup_stores_visible();
+  float2* st = stats + (int64_t)r * ((V + 15) / 16);
+  auto repair = [&](int w) {
+    const int sl = w >> 4, c0 = sl * 16;
+    float v[16], mx = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      v[u] = c0 + u < V ? x[c0 + u] : -INFINITY;
+      mx = fmaxf(mx, v[u]);
+    }
+    float q[4];  // the epilogue's order: four columns per lane, then the two xor-shuffles
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      q[g] = 0.f;
+#pragma unroll
+      for (int u = 4 * g; u < 4 * g + 4; ++u) q[g] += mx > -INFINITY ? __expf(v[u] - mx) : 0.f;  // (never NaN)
+    }
+    st[sl] = float2{mx, (q[0] + q[1]) + (q[2] + q[3])};
+  };
+  constrain_visit(e, V, t, c, lane, repair, repair);
+}
+
+void constrain_logits(float* logits, float2* stats, int R, int V, const int32_t* ids, int64_t ids_ld, int t,
+                      const DecodeConstraints& c, hipStream_t s) {
+  require(logits && ids && R >= 1 && V >= 1, "constrain_logits: need logits, ids and R, V >= 1");
+  require(t >= 0 && t < ids_ld, "constrain_logits: t must be in [0, ids_ld)");
+  require(c.no_repeat_ngram >= 0, "constrain_logits: no_repeat_ngram must be >= 0");
+  require(c.end_id >= -1 && c.end_id < V, "constrain_logits: end_id must be in [-1, num_vocab)");
+  require(c.min_length >= 0 && (c.min_length == 0 || c.end_id >= 0),
+          "constrain_logits: min_length must be >= 0 and needs an end_id");
+  require(c.repetition_penalty > 0.f && c.repetition_penalty < INFINITY,
+          "constrain_logits: repetition_penalty must be finite and > 0");  // (false for a NaN)
+  require(c.n_banned >= 0 && c.n_banned <= 1024 && (c.n_banned == 0 || c.banned),
+          "constrain_logits: n_banned must be in [0, 1024], with a banned list");
+  if (hz::active()) {
+    using namespace hz;
+    op(s, "constrain_logits", {rd(ids, (int64_t)R * ids_ld * 4), rd(c.banned, (int64_t)c.n_banned * 4),
+                               wr(logits, (int64_t)R * V * 4), wr(stats, stats ? (int64_t)R * ((V + 15) / 16) * 8 : 0)});
+  }
+  constrain_logits_kernel<<<R, 64, 0, s>>>(logits, stats, V, ids, ids_ld, t, c);
   CAPGEN_HIP(hipGetLastError());
 }
 

@@ -204,6 +204,32 @@ int capgen_sample_nucleus(capgen_t* h, const void* feats, int feats_dtype, const
                           int n_samples, float temperature, int top_k, float top_p, uint64_t seed, int64_t* ids_out,
                           float* logp_out, void* stream);
 
+/* Decode constraints of capgen_beam_nbest and capgen_sample / capgen_sample_nucleus: before every step's
+ * selection the row's logits are edited from its own emitted tokens e (everything after <START>), in this
+ * order: (1) repetition_penalty theta: every distinct word w of e gets z[w] / theta if z[w] > 0, else
+ * z[w] * theta, once; (2) every banned word gets -inf; (3) min_length m: end_id gets -inf while the caption
+ * would end with fewer than m tokens (<END> included); (4) no_repeat_ngram n: every word that would complete
+ * an n-gram already in e gets -inf (n = 1: every emitted word).  A blocked word has probability exactly 0;
+ * softmax, log-softmax, top-k, nucleus mass and logp_out are taken over what is left.  One more launch per
+ * step while any constraint is on, none otherwise; capgen_greedy and capgen_beam (the reference's decoders)
+ * are never constrained.  Finished beam hypotheses are not affected; capgen_sample keeps drawing (and
+ * blocking) after <END>.  Constraints make sampled roll-outs off-policy: the trainers leave them off.
+ * Definition: csrc/select.hip.
+ * The setter copies the struct and the banned list; NULL switches every constraint off (the default).  It
+ * fails, naming the argument, outside the ranges below and unless num_vocab - n_banned - max_length >= 16
+ * (every row keeps at least 16 finite logits, the most a selection takes).  capgen_beam_nbest fails while
+ * min_length > 0 and the struct's end_id differs from its own.
+ * Added without a change of CAPGEN_ABI_VERSION: no existing entry changed (backward compatible). */
+typedef struct capgen_decode_constraints {
+  int32_t no_repeat_ngram;     /* 0 = off, else in [1, max_length) */
+  int32_t min_length;          /* 0 = off, else in [1, max_length - 1]; needs end_id */
+  int32_t end_id;              /* [-1, num_vocab) */
+  float   repetition_penalty;  /* finite, > 0; 1 = off */
+  const int32_t* banned;       /* HOST array, copied by the call */
+  int32_t n_banned;            /* [0, 1024], every id in [0, num_vocab) */
+} capgen_decode_constraints;
+int capgen_set_decode_constraints(capgen_t* h, const capgen_decode_constraints* c);
+
 /* Decode scoring of capgen_greedy / capgen_beam: 0 (default) = Transformer (argmax of Softmax,
  * beams accumulate probabilities, model.py:124-128,183); 1 = PolicyNetwork, the SCST model
  * (argmax of LogSoftmax, beams accumulate log-probabilities, model_RL.py:72,126-127,157,182). */
@@ -513,6 +539,12 @@ int capgen_debug_beam_step_ended(const float* logits, const void* stats, const f
 int capgen_debug_beam_finish(const int64_t* seq, const float* logp, const int32_t* len, int k, int B, int Tw,
                              float length_penalty, int n_best, int64_t* ids_out, float* score_out, float* logp_out,
                              int32_t* len_out, void* stream);
+/* The decode constraints' one launch on device logits [R][V] (edited in place) before the selection of
+ * position t: row r's history is ids[r * ids_ld + 1 .. t] (device, t < ids_ld); stats (nullable): the rows'
+ * slab stats [R][ceil(V / 16)] of capgen_debug_gemm_classifier, rebuilt for every slab an edit touched.
+ * c as capgen_set_decode_constraints takes it (banned on the host), without the max_length ranges. */
+int capgen_debug_constrain_logits(float* logits, void* stats, int R, int V, const int32_t* ids, int64_t ids_ld,
+                                  int t, const capgen_decode_constraints* c, void* stream);
 /* SCST kernels (csrc/rl.hip): rows = sample (argmax log-softmax), lse, logp[sample], entropy per logit
  * row; image = per-image masked mean entropy, scal[0] = sum(mask); numer: scal[1] = -sum logp mask
  * score; loss: out = {(1-w) lm + w struct, lm, struct}; grad = the fully scaled d loss / d logits. */

@@ -8,6 +8,9 @@ sampling).  The random-init weights give nearly flat logits, the worst case of t
 beam5e / beam5en: the beam search that stops at <END> (Engine.beam_nbest, beam 5, <END> = id 2) with
 length_penalty 0 and n_best 1 / length_penalty 1 and n_best 5 -- beam5's launches plus one finish kernel, read
 against beam5 of the same run.
+beam5ec / sample1c: beam5e / sample1 under decode constraints (Engine.set_decode_constraints: no_repeat_ngram 2,
+min_length 5, repetition_penalty 1.2, three banned words) -- one more launch per decode step, read against
+beam5e / sample1 of the same run.
 
 Algorithmic work (KV-cached count): beam-5 1776.7 GFLOP, greedy 699.4 GFLOP per
 256-image batch.  The reference CPU path (no KV cache) took 25.0 s (beam) / 5.87 s (greedy) per
@@ -28,7 +31,8 @@ from capgen.params import reference_init_state_dict  # noqa: E402
 from capgen.synthetic import synthetic_batch  # noqa: E402
 
 GFLOP = {"beam5": 1776.7, "greedy": 699.4, "sample1": 699.4, "sample5": 1776.7,  # (sampleN: its decode steps')
-         "sample1p": 699.4, "sample5p": 1776.7, "beam5e": 1776.7, "beam5en": 1776.7}
+         "sample1p": 699.4, "sample5p": 1776.7, "beam5e": 1776.7, "beam5en": 1776.7,
+         "beam5ec": 1776.7, "sample1c": 699.4}
 
 
 def main():
@@ -36,7 +40,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1, help="untimed calls first (the first one tunes GEMM shapes and sizes the workspaces)")
-    ap.add_argument("--modes", default="beam5,greedy", help="of beam5, greedy, sample1, sample5, sample1p, sample5p, beam5e, beam5en")
+    ap.add_argument("--modes", default="beam5,greedy", help="of beam5, greedy, sample1, sample5, sample1p, sample5p, beam5e, beam5en, beam5ec, sample1c")
     args = ap.parse_args()
     cfg = preset("C2", dtype="bf16")
     dev = torch.device("cuda", 0)
@@ -53,10 +57,16 @@ def main():
             "sample1p": lambda: eng.sample(f, p, n_samples=1, seed=1, top_p=0.9),
             "sample5p": lambda: eng.sample(f, p, n_samples=5, seed=1, top_p=0.9),
             "beam5e": lambda: eng.beam_nbest(f, p, 5, 2, length_penalty=0.0, n_best=1),
-            "beam5en": lambda: eng.beam_nbest(f, p, 5, 2, length_penalty=1.0, n_best=5)}
+            "beam5en": lambda: eng.beam_nbest(f, p, 5, 2, length_penalty=1.0, n_best=5),
+            "beam5ec": lambda: eng.beam_nbest(f, p, 5, 2, length_penalty=0.0, n_best=1),
+            "sample1c": lambda: eng.sample(f, p, n_samples=1, seed=1)}
     for name, fn in runs.items():
         if name not in args.modes.split(","):
             continue
+        if name.endswith("c"):
+            eng.set_decode_constraints(no_repeat_ngram=2, min_length=5, end_id=2, repetition_penalty=1.2, banned=(0, 1, 3))
+        else:
+            eng.set_decode_constraints()
         for _ in range(args.warmup):
             fn()
         torch.cuda.synchronize()
