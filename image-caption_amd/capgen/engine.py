@@ -316,6 +316,37 @@ class Engine:
                                                 _stream(self.device)))
         return out
 
+    def score_captions(self, feats, pos, caps, img_idx=None):
+        """Log-probabilities of given captions caps [R, T] under the model (capgen_score_captions): the
+        teacher-forced forward with dropout off, read out per token.  Targets are caps[:, 1:]; a pad
+        target scores exactly 0 and does not count.  img_idx [R] given: feats / pos are [n_images, N, .]
+        and row r reads image img_idx[r], so several candidates per image share one copy of the
+        features; None: feats / pos are [R, N, .].  Returns (token_logp [R, T-1] f32, logp [R] f32,
+        length [R] int32, hits [R] int32) on the engine's device; hits counts the kept positions whose
+        target is the teacher-forced argmax.  Nothing of the engine's training state changes."""
+        dev = self.device
+        c = torch.as_tensor(caps).to(dev, dtype=torch.int32, non_blocking=True).contiguous()
+        if c.dim() != 2:
+            raise ValueError("capgen: captions must be [R, T]")
+        R, T = c.shape
+        if img_idx is None:
+            f, ft, p, _ = self._inputs(feats, pos, c)
+            idx, n_img = None, 0
+        else:
+            f, ft, p, _ = self._inputs(feats, pos)
+            idx = torch.as_tensor(img_idx).to(dev, dtype=torch.int32).contiguous()
+            if idx.shape != (R,):
+                raise ValueError("capgen: img_idx must be [R]")
+            n_img = f.shape[0]
+        tok = torch.empty(R, max(T - 1, 0), dtype=torch.float32, device=dev)
+        logp = torch.empty(R, dtype=torch.float32, device=dev)
+        length = torch.empty(R, dtype=torch.int32, device=dev)
+        hits = torch.empty(R, dtype=torch.int32, device=dev)
+        _lib.check(self.lib.capgen_score_captions(self.h, _ptr(f), ft, _ptr(p), n_img, _ptr(idx), _ptr(c), R,
+                                                  f.shape[1], T, _ptr(tok), _ptr(logp), _ptr(length), _ptr(hits),
+                                                  _stream(self.device)))
+        return tok, logp, length, hits
+
     def logits(self, B, T):
         out = torch.empty(B * (T - 1), self.cfg.num_vocab, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.capgen_copy_logits(self.h, _ptr(out), out.numel(), _stream(self.device)))

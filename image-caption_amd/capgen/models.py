@@ -115,6 +115,40 @@ class MODEL_init:
         logprob = sequence_logprob(ids[..., 1:logp.shape[-1] + 1], logp, end)
         return [self.decode_captions(host[j]) for j in range(host.shape[0])], logprob
 
+    def score_captions(self, object_features, position_features, captions, length_penalty=0.0):
+        """How likely are these captions for these images: the log-probability of given caption ids under
+        the model (teacher-forced, temperature 1, unconstrained, dropout off whatever the train/eval state;
+        nothing is updated).  captions: [B, T] ids, one per image, or [n, B, T], n candidates per image (the
+        features are read through an image index: one copy serves all n); tensor or numpy, <START> first,
+        padded with <NULL> after <END> (utils.rollout_captions turns decoded ids into this form).  Returns a
+        dict of tensors on the model's device, shaped like the input without T: 'logp' (the sum of the
+        token log-probabilities through <END>), 'score' = logp / max(length, 1) ** length_penalty
+        (beam_captions' formula), 'token_logp' [..., T-1] (0 at pad targets), 'length' (non-pad targets,
+        int32) and 'token_accuracy' = the share of them that are the teacher-forced argmax."""
+        caps = torch.as_tensor(captions)
+        if caps.dim() not in (2, 3):
+            raise ValueError("capgen: captions must be [B, T] or [n, B, T] ids")
+        if len(object_features.shape) != 3 or len(position_features.shape) != 3:
+            raise ValueError("capgen: object_features [B, N, F] and position_features [B, N, P] are needed")
+        B = int(object_features.shape[0])
+        if caps.shape[-2] != B or int(position_features.shape[0]) != B:
+            raise ValueError("capgen: captions must have the batch of the features")
+        T = int(caps.shape[-1])
+        if T < 2 or T > self.config.max_length:
+            raise ValueError("capgen: captions need 2 <= T <= max_length")
+        eng = self.model.engine
+        if caps.dim() == 2:
+            tok, logp, length, hits = eng.score_captions(object_features, position_features, caps)
+        else:
+            n = int(caps.shape[0])
+            idx = torch.arange(B, dtype=torch.int32).repeat(n)
+            tok, logp, length, hits = eng.score_captions(object_features, position_features, caps.reshape(n * B, T),
+                                                         img_idx=idx)
+            tok, logp, length, hits = tok.view(n, B, T - 1), logp.view(n, B), length.view(n, B), hits.view(n, B)
+        denom = length.clamp(min=1).to(torch.float32)
+        return {"logp": logp, "score": logp / denom ** float(length_penalty), "token_logp": tok, "length": length,
+                "token_accuracy": hits.to(torch.float32) / denom}
+
     def decode_captions(self, caption_vector):
         return decode_captions(caption_vector, self.idx_to_word)
 

@@ -102,7 +102,17 @@ struct StepIn {
   // per-caption loss weights [B] (capgen_train_step_weighted): forward()'s CE scales caption b's loss
   // rows and logit gradients by w[b]; the count stays the number of non-pad targets
   const float* w = nullptr;
-  bool operator==(const StepIn& o) const { return idx == o.idx && n_img == o.n_img && w == o.w; }
+  // score mode (capgen_score_captions): forward()'s classifier section ends in score_finish / score_rows,
+  // which write these, in place of the CE kernels, loss_finalize and every collective; dropout is off
+  bool score = false;
+  float* s_tok = nullptr;    // [B, T-1] token log-probabilities, or null
+  float* s_logp = nullptr;   // [B]
+  int32_t* s_len = nullptr;  // [B] or null
+  int32_t* s_hits = nullptr;  // [B] or null
+  bool operator==(const StepIn& o) const {
+    return idx == o.idx && n_img == o.n_img && w == o.w && score == o.score && s_tok == o.s_tok &&
+           s_logp == o.s_logp && s_len == o.s_len && s_hits == o.s_hits;
+  }
 };
 
 struct EncAct {
@@ -137,6 +147,8 @@ struct Acts {
   void* dlogits;
   float2* ce_stats;  // fused classifier + CE (bf16): {max, sum exp} per row and 16-column slab
   float* ce_tl;      // its target logits
+  float* sc_tok;     // score mode, logits path: per-row log-probability when the caller wants none ...
+  int32_t* sc_hit;   // ... and per-row hits, read by the per-caption pass
   float *loss_row, *grad_scale, *loss, *loss_ce;
   void* gEnc;     // encoder-chain residual gradient while decoder block 0 finishes on es2 (overlap_dec0)
   // SCST (rl.hip): per-row sample / lse / logp[sample] / entropy, per-image entropy, scalars
@@ -829,6 +841,9 @@ struct capgen_engine {
       T_(gb.gATT2, Md * dd);
       T_(gb.gQc, Md * dd);
     }
+    // score mode's per-row scratch, last: every buffer of the train step keeps its offset
+    p.take(a.sc_tok, Md);
+    p.take(a.sc_hit, Md);
   }
   const Layout& L_() const { return L; }
 
@@ -963,7 +978,7 @@ struct capgen_engine {
     // stays on the critical stream) the prep runs there too, first thing of the front
     const bool caps_front = overlap_front && es2 != s && !comm;
     if (!caps_front) prepare_captions(caps, B, T, cfg.pad_idx, a.ids, a.tgt, a.count, s, nullptr, defer ? a.grad_scale : nullptr);
-    if (comm) {
+    if (comm && !in.score) {  // (scoring is rank-local: no collective, and the count is not read)
       if (count_override) {
         if (hz::active()) hz::op(s, "count_copy", {hz::wr(a.count, 4)});
         CAPGEN_HIP(hipMemcpyAsync(a.count, count_host, sizeof(float), hipMemcpyHostToDevice, s));
@@ -1036,6 +1051,9 @@ struct capgen_engine {
     if (L.has_mf)
       move_first_fwd(a.D[L.Ld], a.X[L.Le], Md, Lq, 0, N, a.mfU, a.mfH, a.tmp, a.mfOut, /*keep=*/true, drop_on, s);
     // ---- classifier + CE (model.py:93-96) ----
+    // score mode (capgen_score_captions): the same classifier, then a read-out that writes B + Md numbers
+    // in place of the CE rows -- no softmax - onehot, no loss word, no gradient scale, no collective
+    require(!in.score || (!drop_on && !defer), "forward: score mode runs without dropout and writes no loss");
     if (fused_ce()) {
       // the logits are never written: the GEMM epilogue leaves exp(v - slab max) + slab stats,
       // ce_finish turns them into the loss rows and softmax - onehot (model.py:93-96)
@@ -1045,11 +1063,23 @@ struct capgen_engine {
       ga.ce_stats = a.ce_stats, ga.ce_ld = (L.V + 15) / 16, ga.ce_tgt = a.tgt, ga.ce_tlogit = a.ce_tl;
       if (stamp_on) ga.stamp = stamp(s, "gemm classifier+CE " + dims(Md, L.V, dd));
       gemm(ga, act, act, false, false, s);
-      ce_finish(a.ce_stats, (L.V + 15) / 16, a.ce_tl, a.tgt, Md, L.V, cfg.pad_idx, a.loss_row,
-                reinterpret_cast<bf16*>(a.dlogits), s, in.w, Lq);
+      if (in.score)
+        score_finish(a.ce_stats, (L.V + 15) / 16, a.ce_tl, a.tgt, Md, L.V, cfg.pad_idx, Lq, in.s_tok, nullptr,
+                     in.s_logp, in.s_len, in.s_hits, s);
+      else
+        ce_finish(a.ce_stats, (L.V + 15) / 16, a.ce_tl, a.tgt, Md, L.V, cfg.pad_idx, a.loss_row,
+                  reinterpret_cast<bf16*>(a.dlogits), s, in.w, Lq);
     } else {
       linear(dec_out(), dd, L.Wc, dd, a.logits, L.V, DType::F32, Md, L.V, dd, P(L.bc), 0, s);
-      cross_entropy_rows(a.logits, a.tgt, Md, L.V, cfg.pad_idx, a.loss_row, a.dlogits, act, s, in.w, Lq);
+      if (in.score)
+        score_rows(a.logits, a.tgt, Md, L.V, cfg.pad_idx, Lq, in.s_tok ? in.s_tok : a.sc_tok, a.sc_hit, in.s_logp,
+                   in.s_len, in.s_hits, s);
+      else
+        cross_entropy_rows(a.logits, a.tgt, Md, L.V, cfg.pad_idx, a.loss_row, a.dlogits, act, s, in.w, Lq);
+    }
+    if (in.score) {
+      stamp_fwd_end = stamp_next;
+      return;
     }
     float* lo = loss_out ? loss_out : a.loss;
     last_loss = lo;
@@ -2673,6 +2703,47 @@ int capgen_train_step_weighted(capgen_t* h, const void* feats, int feats_dtype, 
       h->forward(feats, ft, pos, caps, B, N, T, loss_out, h->training, h->es);
       h->leave(cs);
     }
+  });
+}
+
+int capgen_score_captions(capgen_t* h, const void* feats, int feats_dtype, const float* pos, int n_images,
+                          const int32_t* img_idx, const int32_t* caps, int R, int N, int T, float* token_logp,
+                          float* logp, int32_t* length, int32_t* hits, void* stream) {
+  return guarded([&] {
+    set_device(h);
+    require(feats && pos && caps, "score_captions: feats, pos or caps is null");
+    require(logp != nullptr, "score_captions: logp is null");
+    require(R >= 1 && N >= 1 && N <= 64, "score_captions: need R >= 1 and 1 <= N <= 64");
+    require(T >= 2 && T <= h->L.maxlen, "score_captions: need 2 <= T <= max_length");
+    require(!img_idx || n_images >= 1, "score_captions: empty store");
+    hipStream_t cs = (hipStream_t)stream;
+    StepIn si;
+    si.idx = img_idx, si.n_img = img_idx ? n_images : 0;
+    si.score = true, si.s_tok = token_logp, si.s_logp = logp, si.s_len = length, si.s_hits = hits;
+    Scoped<StepIn> inputs(h->in, si);
+    // eager, on the engine's stream: the cached training graphs (keyed without the mode) stay as they are;
+    // a deferred loss of the previous step was issued by that step's backward, which es is ordered after
+    h->ensure_acts(R, N, T);
+    h->enter(cs);
+    h->forward(feats, dt(feats_dtype), pos, caps, R, N, T, nullptr, /*drop_on=*/false, h->es);
+    h->leave(cs);
+  });
+}
+
+int capgen_debug_score_rows(const float* logits, const int32_t* tgt, int M, int V, int pad, int rows_per_caption,
+                            float* token_logp, int32_t* hit, float* logp, int32_t* length, int32_t* hits,
+                            void* stream) {
+  return guarded([&] {
+    score_rows(logits, tgt, M, V, pad, rows_per_caption, token_logp, hit, logp, length, hits, (hipStream_t)stream);
+  });
+}
+
+int capgen_debug_score_finish(const void* stats, int64_t ld, const float* tlogit, const int32_t* tgt, int M, int V,
+                              int pad, int rows_per_caption, float* token_logp, int32_t* hit, float* logp,
+                              int32_t* length, int32_t* hits, void* stream) {
+  return guarded([&] {
+    score_finish(reinterpret_cast<const float2*>(stats), ld, tlogit, tgt, M, V, pad, rows_per_caption, token_logp,
+                 hit, logp, length, hits, (hipStream_t)stream);
   });
 }
 

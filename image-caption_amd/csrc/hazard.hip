@@ -106,7 +106,10 @@ void reset() {
   std::lock_guard<std::mutex> lk(S.mu);
   S.ops.clear();
   S.eclk.clear();
-  for (auto& c : S.sclk) c = Clock{};
+  // the streams too: with the log empty and every clock zero their numbers mean nothing, and a process that
+  // checks many engines one after another (the test suite) would otherwise run out of the kMaxStreams slots
+  S.sid.clear();
+  S.sclk.clear();
   S.host = Clock{};
 }
 

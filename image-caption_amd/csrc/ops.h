@@ -81,6 +81,20 @@ void cross_entropy_rows(const float* logits, const int32_t* tgt, int M, int V, i
 // epilogue (GemmArgs::ce_stats); writes loss_row and rewrites dl as softmax - onehot (0 for pad)
 void ce_finish(const float2* stats, int64_t ld, const float* tlogit, const int32_t* tgt, int M, int V, int pad,
                float* loss_row, bf16* dl, hipStream_t s, const float* row_w = nullptr, int rows_per_w = 1);
+// Scoring given captions (no backward): token_logp[m] = logit[m][tgt] - logsumexp(logit[m]) and hit[m] =
+// (the target's logit is >= every logit of the row), both exactly 0 where tgt == pad; caption r = rows
+// [r * rows_per_caption, (r + 1) * rows_per_caption): logp[r] = sum of its token_logp in a fixed order (no
+// atomics), length[r] = its non-pad targets, hits[r] = sum of its hits.  Neither writes anything of size
+// M x V.  length / hits may be null.
+// score_rows: from f32 logits [M][V] (token_logp and hit [M] are required: the per-caption pass reads them)
+void score_rows(const float* logits, const int32_t* tgt, int M, int V, int pad, int rows_per_caption,
+                float* token_logp, int32_t* hit, float* logp, int32_t* length, int32_t* hits, hipStream_t s);
+// score_finish: from the fused classifier's slab statistics and target logits (GemmArgs::ce_stats, ce_tlogit;
+// V % 4 == 0, ld >= ceil(V / 16), statistics at or beyond slab ceil(V / 16) of a row are not read); the e rows
+// the GEMM left are no argument.  token_logp / hit may be null too.
+void score_finish(const float2* stats, int64_t ld, const float* tlogit, const int32_t* tgt, int M, int V, int pad,
+                  int rows_per_caption, float* token_logp, int32_t* hit, float* logp, int32_t* length,
+                  int32_t* hits, hipStream_t s);
 // loss = sum(loss_row)/count (or FocalLoss of it); grad_scale = dloss/d(logit sums).
 // ce_in: the mean CE is given (all-reduced partials); partial: write sum(loss_row)/count only;
 // grad_scale null: the loss only (the scale was written elsewhere, e.g. by prepare_captions).

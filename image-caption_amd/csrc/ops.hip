@@ -759,6 +759,201 @@ void ce_finish(const float2* stats, int64_t ld, const float* tlogit, const int32
   CAPGEN_HIP(hipGetLastError());
 }
 
+// ---- scoring given captions: per-row log-probability and teacher-forced hit, per-caption sums ---------
+// The forward's read-out without a backward: nothing of size M x V is written, no loss word.
+// One workgroup per row, as the CE kernels: the row's max / sum-exp come from ONE pass (register form:
+// the row loaded once as float4s, clamped addresses, no branch around a load; generic form: a running
+// {max, sum} per thread), the target logit from one more 4-byte load issued with them.
+__device__ __forceinline__ void score_row_write(int m, int y, int pad, float tl, float mx, float se,
+                                                float* __restrict__ token_logp, int32_t* __restrict__ hit) {
+  const bool kept = y != pad;
+  token_logp[m] = kept ? tl - (mx + logf(se)) : 0.f;
+  hit[m] = kept && tl >= mx ? 1 : 0;
+}
+template <int NV4>
+__global__ void __launch_bounds__(256) score_reg_kernel(const float* __restrict__ logits, const int32_t* __restrict__ tgt,
+                                                        int V, int pad, float* __restrict__ token_logp,
+                                                        int32_t* __restrict__ hit) {
+  __shared__ float sh[4];
+  const int m = blockIdx.x, V4 = V >> 2;
+  const float4* x = reinterpret_cast<const float4*>(logits + (int64_t)m * V);
+  const int y = tgt[m];
+  float4 v[NV4];
+#pragma unroll
+  for (int u = 0; u < NV4; ++u) v[u] = x[min((int)threadIdx.x + 256 * u, V4 - 1)];
+  const float tl = logits[(int64_t)m * V + min(max(y, 0), V - 1)];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int u = 0; u < NV4; ++u) {
+    if ((int)threadIdx.x + 256 * u >= V4) v[u] = float4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    mx = fmaxf(mx, fmaxf(fmaxf(v[u].x, v[u].y), fmaxf(v[u].z, v[u].w)));
+  }
+  mx = block_max(mx, sh);
+  float se = 0.f;
+#pragma unroll
+  for (int u = 0; u < NV4; ++u)
+    se += (expf(v[u].x - mx) + expf(v[u].y - mx)) + (expf(v[u].z - mx) + expf(v[u].w - mx));
+  se = block_sum_pairwise(se, sh);
+  if (threadIdx.x == 0) score_row_write(m, y, pad, tl, mx, se, token_logp, hit);
+}
+__global__ void __launch_bounds__(256) score_gen_kernel(const float* __restrict__ logits, const int32_t* __restrict__ tgt,
+                                                        int V, int pad, float* __restrict__ token_logp,
+                                                        int32_t* __restrict__ hit) {
+  __shared__ float sh[4];
+  const int m = blockIdx.x;
+  const float* x = logits + (int64_t)m * V;
+  const int y = tgt[m];
+  const float tl = x[min(max(y, 0), V - 1)];
+  float tm = -INFINITY, ts = 0.f;  // the thread's running max and sum exp(x - tm)
+  for (int c = threadIdx.x; c < V; c += 256) {
+    const float xv = x[c];
+    if (xv > tm) ts = ts * expf(tm - xv) + 1.f, tm = xv;  // (tm = -inf: ts = 0 * 0 + 1)
+    else if (xv > -INFINITY) ts += expf(xv - tm);
+  }
+  const float mx = block_max(tm, sh);
+  const float se = block_sum_pairwise(ts == 0.f ? 0.f : ts * expf(tm - mx), sh);
+  if (threadIdx.x == 0) score_row_write(m, y, pad, tl, mx, se, token_logp, hit);
+}
+// caption r = rows [r * Lq, (r + 1) * Lq): logp = their token_logp added in row order, length = kept
+// rows, hits = their hits.  One thread per caption, a fixed order: two runs give the same bits.
+__global__ void __launch_bounds__(256) score_caption_kernel(const float* __restrict__ token_logp,
+                                                            const int32_t* __restrict__ hit,
+                                                            const int32_t* __restrict__ tgt, int R, int Lq, int pad,
+                                                            float* __restrict__ logp, int32_t* __restrict__ length,
+                                                            int32_t* __restrict__ hits) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  float acc = 0.f;
+  int n = 0, h = 0;
+  for (int t = 0; t < Lq; ++t) {
+    const int m = r * Lq + t;
+    acc += token_logp[m];
+    n += tgt[m] != pad;
+    h += hit[m];
+  }
+  logp[r] = acc;
+  if (length) length[r] = n;
+  if (hits) hits[r] = h;
+}
+static void check_score_args(const char* who, const void* a, const void* b, const int32_t* tgt, int M, int V,
+                             int rows_per_caption, const float* logp) {
+  const std::string w(who);
+  require(a && b && tgt && logp, w + ": a null input or logp");
+  require(M >= 1 && V >= 1, w + ": M and V must be >= 1");
+  require(rows_per_caption >= 1 && M % rows_per_caption == 0, w + ": rows_per_caption must be >= 1 and divide M");
+}
+void score_rows(const float* logits, const int32_t* tgt, int M, int V, int pad, int rows_per_caption,
+                float* token_logp, int32_t* hit, float* logp, int32_t* length, int32_t* hits, hipStream_t s) {
+  check_score_args("score_rows", logits, token_logp, tgt, M, V, rows_per_caption, logp);
+  require(hit != nullptr, "score_rows: hit is null");
+  const int R = M / rows_per_caption;
+  if (hz::active()) {
+    using namespace hz;
+    op(s, "score_rows", {rd(logits, (int64_t)M * V * 4), rd(tgt, (int64_t)M * 4), wr(token_logp, (int64_t)M * 4),
+                         wr(hit, (int64_t)M * 4)});
+    op(s, "score_caption", {rd(token_logp, (int64_t)M * 4), rd(hit, (int64_t)M * 4), rd(tgt, (int64_t)M * 4),
+                            wr(logp, (int64_t)R * 4), wr(length, (int64_t)R * 4), wr(hits, (int64_t)R * 4)});
+  }
+  if (V % 4 == 0 && V <= 1024 * 16) {  // ce_reg_kernel's condition and its register forms
+    const int nv4 = (V / 4 + 255) / 256;
+    if (nv4 <= 4) score_reg_kernel<4><<<M, 256, 0, s>>>(logits, tgt, V, pad, token_logp, hit);
+    else if (nv4 <= 8) score_reg_kernel<8><<<M, 256, 0, s>>>(logits, tgt, V, pad, token_logp, hit);
+    else if (nv4 <= 10) score_reg_kernel<10><<<M, 256, 0, s>>>(logits, tgt, V, pad, token_logp, hit);
+    else score_reg_kernel<16><<<M, 256, 0, s>>>(logits, tgt, V, pad, token_logp, hit);
+  } else {
+    score_gen_kernel<<<M, 256, 0, s>>>(logits, tgt, V, pad, token_logp, hit);
+  }
+  score_caption_kernel<<<(R + 255) / 256, 256, 0, s>>>(token_logp, hit, tgt, R, rows_per_caption, pad, logp, length,
+                                                      hits);
+  CAPGEN_HIP(hipGetLastError());
+}
+
+// The fused classifier's read-out (GemmArgs::ce_stats): a row's log-probability needs only its V / 16
+// {mx_c, s_c} pairs and the target logit -- the e rows are not an argument.  One workgroup per caption,
+// one wave per row (waves stride the caption's rows): a lane holds SPT pairs (8-byte loads: with an odd
+// ld, 625 at V = 10000, rows start 8-byte aligned only), every load of the row issued up front from
+// clamped addresses below the row's slab count, then lse = mx + log sum_c s_c exp(mx_c - mx) by
+// cross-lane shuffles.  Wave w adds its rows' log-probabilities in row order, thread 0 the waves' sums in
+// wave order: a fixed order, no atomics.
+constexpr int SCORE_WAVES = 8;
+template <int SPT>
+__global__ void __launch_bounds__(64 * SCORE_WAVES) score_finish_kernel(
+    const float2* __restrict__ stats, int64_t ld, const float* __restrict__ tlogit, const int32_t* __restrict__ tgt,
+    int V, int pad, int Lq, float* __restrict__ token_logp, int32_t* __restrict__ hit, float* __restrict__ logp,
+    int32_t* __restrict__ length, int32_t* __restrict__ hits) {
+  __shared__ float sh_lp[SCORE_WAVES];
+  __shared__ int sh_n[SCORE_WAVES], sh_h[SCORE_WAVES];
+  const int r = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nsl = (V + 15) / 16;
+  float acc = 0.f;
+  int n = 0, h = 0;
+  for (int t = wv; t < Lq; t += SCORE_WAVES) {  // (uniform per wave)
+    const int m = r * Lq + t;
+    const int y = tgt[m];
+    const float tl = tlogit[m];
+    float2 st[SPT];
+#pragma unroll
+    for (int u = 0; u < SPT; ++u) st[u] = stats[(int64_t)m * ld + min(lane + 64 * u, nsl - 1)];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < SPT; ++u) {
+      if (lane + 64 * u >= nsl) st[u] = float2{-INFINITY, 0.f};
+      mx = fmaxf(mx, st[u].x);
+    }
+    mx = wave_max(mx);
+    float se = 0.f;
+#pragma unroll
+    for (int u = 0; u < SPT; ++u) se += st[u].y == 0.f ? 0.f : st[u].y * expf(st[u].x - mx);
+    se = wave_sum(se);
+    const bool kept = y != pad;
+    const float lp = kept ? tl - (mx + logf(se)) : 0.f;
+    const int hm = kept && tl >= mx ? 1 : 0;
+    if (lane == 0) {
+      if (token_logp) token_logp[m] = lp;
+      if (hit) hit[m] = hm;
+    }
+    acc += lp, n += kept, h += hm;
+  }
+  if (lane == 0) sh_lp[wv] = acc, sh_n[wv] = n, sh_h[wv] = h;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float a = sh_lp[0];
+    int nn = sh_n[0], hh = sh_h[0];
+#pragma unroll
+    for (int w = 1; w < SCORE_WAVES; ++w) a += sh_lp[w], nn += sh_n[w], hh += sh_h[w];
+    logp[r] = a;
+    if (length) length[r] = nn;
+    if (hits) hits[r] = hh;
+  }
+}
+void score_finish(const float2* stats, int64_t ld, const float* tlogit, const int32_t* tgt, int M, int V, int pad,
+                  int rows_per_caption, float* token_logp, int32_t* hit, float* logp, int32_t* length,
+                  int32_t* hits, hipStream_t s) {
+  check_score_args("score_finish", stats, tlogit, tgt, M, V, rows_per_caption, logp);
+  require(V % 4 == 0, "score_finish: V must be a multiple of 4");
+  const int nsl = (V + 15) / 16, R = M / rows_per_caption;
+  require(ld >= nsl, "score_finish: ld is smaller than the row's slab count");
+  require(nsl <= 64 * 32, "score_finish: V > 32768");
+  if (hz::active()) {
+    using namespace hz;
+    op(s, "score_finish", {blk(stats, M, (int64_t)nsl * 8, ld * 8, RD), rd(tlogit, (int64_t)M * 4),
+                           rd(tgt, (int64_t)M * 4), wr(token_logp, (int64_t)M * 4), wr(hit, (int64_t)M * 4),
+                           wr(logp, (int64_t)R * 4), wr(length, (int64_t)R * 4), wr(hits, (int64_t)R * 4)});
+  }
+  const int spt = (nsl + 63) / 64;
+  auto go = [&](auto spt_c) {
+    score_finish_kernel<decltype(spt_c)::value><<<R, 64 * SCORE_WAVES, 0, s>>>(
+        stats, ld, tlogit, tgt, V, pad, rows_per_caption, token_logp, hit, logp, length, hits);
+  };
+  if (spt <= 1) go(std::integral_constant<int, 1>{});
+  else if (spt <= 2) go(std::integral_constant<int, 2>{});
+  else if (spt <= 4) go(std::integral_constant<int, 4>{});
+  else if (spt <= 8) go(std::integral_constant<int, 8>{});
+  else if (spt <= 10) go(std::integral_constant<int, 10>{});
+  else if (spt <= 16) go(std::integral_constant<int, 16>{});
+  else go(std::integral_constant<int, 32>{});
+  CAPGEN_HIP(hipGetLastError());
+}
+
 // CE mean over the (global) non-pad count and the FocalLoss transform (model.py:73-76,
 // loss.py:20-28, gamma = 2, applied to the already-averaged CE).  ce_in != null: the mean CE is
 // given (the data-parallel path all-reduces the per-rank partial sums first); partial: only

@@ -312,6 +312,27 @@ int capgen_train_step_weighted(capgen_t* h, const void* feats, int feats_dtype, 
                                const int32_t* img_idx, const int32_t* caps, const float* weights, int B, int N,
                                int T, float* loss_out, int train, void* stream);
 
+/* Score given captions: the teacher-forced forward of capgen_train_step over R caption rows caps [R, T]
+ * (int32), read out as log-probabilities under the model in place of a loss.  Targets are caps[:, 1:];
+ * with pad = pad_idx, Lq = T - 1 and row m = r Lq + t:
+ *   token_logp[r, t] = logit[m, tgt] - logsumexp(logit[m, :]), exactly 0 where tgt == pad   ([R, T-1] f32, or null)
+ *   logp[r]   = sum_t token_logp[r, t], added in a fixed order                              ([R] f32, required)
+ *   length[r] = #{t : tgt != pad}                                                           ([R] int32, or null)
+ *   hits[r]   = #{t : tgt != pad and the target's logit is >= every logit of the row}        ([R] int32, or null)
+ * (the target is then the teacher-forced argmax; ties count).  A caption of pads only gives 0, 0, 0.
+ * img_idx non-null: feats / pos are [n_images, N, .] stores and row r reads image img_idx[r] (n candidates
+ * of one image share its features); img_idx null: feats / pos are [R, N, .] and n_images is ignored.
+ * Temperature 1, never constrained (no decode-constraint state is read or cleared).  Dropout is never
+ * applied and the dropout seed does not advance, whatever capgen_set_training says; no parameter, gradient,
+ * Adam state, gradient scale or loss word is written, and the cached step graphs stay valid (the call runs
+ * eagerly; it re-allocates the activations, as every call does, only when R, N or T exceed every earlier
+ * shape).  Under data parallel the call is rank-local and issues no collective.  focal_loss configs are
+ * scored like any other (the transform belongs to the loss).  Two calls give the same bits.
+ * Added without a change of CAPGEN_ABI_VERSION: no existing entry changed (backward compatible). */
+int capgen_score_captions(capgen_t* h, const void* feats, int feats_dtype, const float* pos, int n_images,
+                          const int32_t* img_idx, const int32_t* caps, int R, int N, int T, float* token_logp,
+                          float* logp, int32_t* length, int32_t* hits, void* stream);
+
 /* Self-critical sequence training (SelfCriticNetwork, models.py:137-211), in two calls with the
  * host scoring the samples in between (CIDEr-D / BLEU, capgen/scst.py):
  *  capgen_rl_sample  replaces PolicyNetwork.forward + .sample (model_RL.py:75-97) and the entropy
@@ -466,6 +487,18 @@ int capgen_debug_cross_entropy_rows_weighted(const float* logits, const int32_t*
 int capgen_debug_ce_finish_weighted(const void* stats, int64_t ld, const float* tlogit, const int32_t* tgt,
                                     const float* row_w, int rows_per_w, int M, int V, int pad, float* loss_row,
                                     void* dl, void* stream);
+/* The two read-outs of capgen_score_captions (ops.h: score_rows from f32 logits [M, V]; score_finish from the
+ * fused classifier's slab statistics [M, ld] {max, sum exp} and target logits, V % 4 == 0, ld >= ceil(V / 16),
+ * nothing at or beyond slab ceil(V / 16) of a row is read).  Per row: token_logp [M] f32, hit [M] int32; per
+ * caption of rows_per_caption rows: logp [M / rows_per_caption] f32, length and hits int32.  length and hits
+ * may be null, for score_finish token_logp and hit too; fail on any other null pointer, rows_per_caption < 1
+ * or M % rows_per_caption != 0.  Neither takes a pointer to softmax / gradient rows. */
+int capgen_debug_score_rows(const float* logits, const int32_t* tgt, int M, int V, int pad, int rows_per_caption,
+                            float* token_logp, int32_t* hit, float* logp, int32_t* length, int32_t* hits,
+                            void* stream);
+int capgen_debug_score_finish(const void* stats, int64_t ld, const float* tlogit, const int32_t* tgt, int M, int V,
+                              int pad, int rows_per_caption, float* token_logp, int32_t* hit, float* logp,
+                              int32_t* length, int32_t* hits, void* stream);
 int capgen_debug_loss_finalize(const float* loss_row, int M, const float* count, int focal, float* loss_out,
                                float* grad_scale, const float* ce_in, int partial, void* stream);
 /* One torch.optim.Adam step of a flat f32 arena (n % 4 == 0): adam_prepare (++*step, device int64; scal =
