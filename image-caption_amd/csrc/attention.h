@@ -1,5 +1,7 @@
 // capgen — masked multi-head attention (forward/backward) launcher interface.
 #pragma once
+#include <cmath>
+
 #include "capgen_common.h"
 #include "gemm.h"
 
@@ -25,6 +27,19 @@ struct AttnGeom {
   Drop drop{};                        // dropout on the probabilities (modules.py:24)
   uint64_t* stamp = nullptr;          // diagnostic timestamps (StampScope)
 };
+
+// the dense attention layout: a batch is rows x leading dimension apart, temperature sqrt(dk)
+inline AttnGeom attn_dense(int B, int H, int Lq, int Lk, int dk, const void* q, int64_t q_ld, const void* k,
+                           int64_t k_ld, const void* v, int64_t v_ld, int64_t o_ld) {
+  AttnGeom g;
+  g.B = B, g.H = H, g.Lq = Lq, g.Lk = Lk, g.dk = dk;
+  g.q = q, g.q_ld = q_ld, g.q_bs = Lq * q_ld;
+  g.k = k, g.k_ld = k_ld, g.k_bs = Lk * k_ld;
+  g.v = v, g.v_ld = v_ld, g.v_bs = Lk * v_ld;
+  g.o_ld = o_ld, g.o_bs = Lq * o_ld;
+  g.temperature = std::sqrt((float)dk);
+  return g;
+}
 
 // probs (optional): [B,H,Lq,Lk] f32, pre-dropout softmax, saved for backward / attention_list.
 void attention_fwd(const AttnGeom& g, void* o, float* probs, DType t, hipStream_t s);

@@ -2,7 +2,7 @@
 through torch.distributed.run; rank r on GPU r).
 
 Each rank trains the fp32 engine through the engine's own RCCL communicator (count all-reduce,
-per-bucket gradient all-reduce or ZeRO-1 reduce-scatter / all-gather, engine.hip) and writes its
+per-bucket gradient all-reduce or ZeRO-1 reduce-scatter / all-gather, engine_update.hip) and writes its
 parameters, losses, checksum and communicator size to <out>.r<rank>.npz.  torch.distributed (gloo)
 is only the bootstrap channel for the unique id.
 

@@ -1,6 +1,6 @@
 """The engine's data-parallel path with several ranks: the RCCL count / partial-CE
 all-reduces and the per-bucket gradient all-reduce (ZERO=0) or ZeRO-1 reduce-scatter + all-gather
-(ZERO=1, the default at world > 1) of engine.hip, run by `world` processes through one communicator.
+(ZERO=1, the default at world > 1) of engine_update.hip, run by `world` processes through one communicator.
 Needs that many GPUs: RCCL refuses two ranks on one device ("Duplicate GPU detected",
 tools/rccl_two_ranks_one_gpu.py on the one-GPU box), so on a one-GPU box these skip --
 except the world-1 runs of the same launcher and worker, which run everywhere.

@@ -188,7 +188,7 @@ def test_forward_graph_equals_eager_fp32(set_knob, dp):
 def test_dp_exact_global_mean_two_half_batch_engines_fp32():
     """SURVEY §8(e) exact-mean rule through the engine's DP path on one GPU: two world-1 RCCL
     engines each run HALF of the batch with capgen_dp_set_global_count(global non-pad count)
-    (engine.hip forward: count override, per-bucket all-reduce, partial-CE all-reduce).  Their
+    (engine_forward.hip / engine_update.hip: count override, per-bucket all-reduce, partial-CE all-reduce).  Their
     losses and fp32 gradients sum to the full-batch engine's (model.py:76 divides by the GLOBAL
     count; averaging per-rank means would not match), and one Adam step on the summed gradients
     gives the full-batch engine's parameters."""
@@ -284,7 +284,7 @@ def _sharded_update_check(cfg, ref, ranks, f, p, c, dtype, steps=2):
 
 @pytest.mark.parametrize("world,dtype", [(2, "fp32"), (8, "fp32"), (4, "bf16")])
 def test_sharded_update_chunks_equal_full_adam(world, dtype):
-    """Sharded update (ZeRO-1, engine.hip bucket_update) at the c2s shape: rank r of `world` runs Adam
+    """Sharded update (ZeRO-1, engine_update.hip bucket_update) at the c2s shape: rank r of `world` runs Adam
     only on chunk r of every gradient bucket (_sharded_update_check)."""
     cfg, seed, z = load_fixture("c2s")
     f, p, c = _inputs(z)
@@ -779,7 +779,7 @@ def test_gemm_register_b_vs_torch(M, N, K, tb, epi):
 
 
 def test_decode_tiles_follow_weight_updates():
-    """The decode step's weight fragment pieces are rebuilt only when the weights moved (engine.hip
+    """The decode step's weight fragment pieces are rebuilt only when the weights moved (engine_decode.hip
     build_dtiles, weight version bumped by every shadow update): decoding, then loading other weights
     (and then one bf16 train step), must decode exactly as a fresh engine holding those weights."""
     from capgen.engine import Engine
@@ -807,7 +807,7 @@ def test_decode_tiles_follow_weight_updates():
 def test_decode_tiles_follow_graph_replayed_steps():
     """Whole-step graph mode (set_graph(True)): from the second step on, Adam runs inside a graph
     replay with no host code, so the weight version the decode tiles key on must move with every
-    replay (engine.hip, `++wver` beside hipGraphLaunch).  Decode after step 1 (tiles built), then
+    replay (engine_step.hip, `++wver` beside hipGraphLaunch).  Decode after step 1 (tiles built), then
     three more replayed steps, then greedy and beam must equal a fresh engine's holding the trained
     weights."""
     from capgen.engine import Engine
