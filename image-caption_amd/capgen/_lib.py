@@ -102,6 +102,12 @@ _SIGS = {
     "capgen_get_lr": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "capgen_set_grad_clip": (C.c_int, [_P, C.c_float]),
     "capgen_last_grad_norm": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "capgen_set_weight_decay": (C.c_int, [_P, C.c_float]),
+    "capgen_set_ema": (C.c_int, [_P, C.c_float]),
+    "capgen_ema_info": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "capgen_get_ema": (C.c_int, [_P, _P, C.c_int64]),
+    "capgen_set_ema_state": (C.c_int, [_P, _P, C.c_int64, C.c_int64]),
+    "capgen_ema_swap": (C.c_int, [_P]),
     "capgen_forward": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "capgen_backward": (C.c_int, [_P, _P]),
     "capgen_adam_step": (C.c_int, [_P, _P]),
@@ -178,6 +184,10 @@ _SIGS = {
     "capgen_debug_adam_scaled": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P,
                                            _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                            C.POINTER(_P), _P, _P]),
+    "capgen_debug_adam_ex": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P,
+                                       C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                       C.POINTER(_P), _P, C.c_float, _P, C.c_float, _P]),
+    "capgen_debug_arena_swap": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
     "capgen_debug_grad_norm": (C.c_int, [_P, C.c_int64, C.c_float, C.c_int, _P, C.c_int, _P, _P]),
     "capgen_debug_to_bf16": (C.c_int, [_P, _P, C.c_int64, _P]),
     "capgen_debug_arena_checksum": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_uint64), _P]),

@@ -6,7 +6,9 @@ libcapgen.so.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import math
 from collections import OrderedDict
 
 import numpy as np
@@ -43,6 +45,15 @@ def check_beam_nbest_args(beam_size, end_id, length_penalty, n_best, num_vocab):
     return int(beam_size), int(n_best)
 
 
+def check_ema_decay(decay) -> float:
+    """Engine.set_ema's argument rule, on the f32 the engine stores (0.99999999 rounds to 1.0f): the value
+    to pass on, 0.0 for off; a ValueError naming the argument otherwise."""
+    d = 0.0 if decay is None else float(np.float32(decay))
+    if not (d == 0.0 or 0.0 < d < 1.0):  # (false for a NaN)
+        raise ValueError(f"capgen: ema decay must be None, 0 or in (0, 1) as an f32, not {decay}")
+    return d
+
+
 class Engine:
     def __init__(self, cfg: CapgenConfig, device="cuda:0"):
         self.cfg = cfg
@@ -59,6 +70,7 @@ class Engine:
         self.h = h
         self.training = True
         self.grad_clip = None  # the max_norm set_grad_clip last set (None: clipping off)
+        self.weight_decay = None  # the value set_weight_decay last set (None: decay off)
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
 
     def close(self):
@@ -111,6 +123,66 @@ class Engine:
         v = C.c_float(0)
         _lib.check(self.lib.capgen_last_grad_norm(self.h, C.byref(v)))
         return v.value
+
+    def set_weight_decay(self, weight_decay: float | None):
+        """Decoupled weight decay as torch.optim.AdamW (capgen_set_weight_decay): every parameter is
+        multiplied by 1 - lr * weight_decay before each update.  None or 0 = off (default); finite, >= 0."""
+        wd = 0.0 if weight_decay is None else float(weight_decay)
+        if not (math.isfinite(wd) and wd >= 0.0):
+            raise ValueError(f"capgen: weight_decay must be finite and >= 0, not {weight_decay}")
+        _lib.check(self.lib.capgen_set_weight_decay(self.h, wd))
+        self.weight_decay = wd or None
+
+    def set_ema(self, decay: float | None):
+        """Keep an exponential moving average of the parameters inside the update kernel
+        (capgen_set_ema; torch.optim.swa_utils.get_ema_multi_avg_fn(decay)): None or 0 = off (default),
+        else 0 < decay < 1.  Off -> on starts the average as a copy of the parameters; on -> on changes
+        the decay only; off keeps the arena readable."""
+        _lib.check(self.lib.capgen_set_ema(self.h, check_ema_decay(decay)))
+
+    def ema_info(self):
+        """(decay as the f32 the engine uses, 0.0 = off; updates issued while on; swapped in?)."""
+        d, n, s = C.c_float(0), C.c_int64(0), C.c_int(0)
+        _lib.check(self.lib.capgen_ema_info(self.h, C.byref(d), C.byref(n), C.byref(s)))
+        return d.value, n.value, bool(s.value)
+
+    def ema_arena(self) -> np.ndarray:
+        """The averaged weights' f32 arena as a host copy (the raw weights while swapped).  After sharded
+        (ZeRO-1) steps: this rank's chunks only until dp_sync_adam_state."""
+        torch.cuda.current_stream(self.device).synchronize()
+        return self._arena_to_host(self.lib.capgen_get_ema)
+
+    def ema_state_dict(self, with_buffer: bool = True):
+        """ema_arena() as reference-named f32 CPU tensors (loadable like state_dict())."""
+        sd = self._unpack(self.ema_arena())
+        if with_buffer:
+            sd[PE_BUFFER] = torch.from_numpy(sinusoid_table(self.cfg.max_length - 1, self.cfg.decode_input_size)[None])
+        return sd
+
+    def set_ema_arena(self, arena: np.ndarray, n_updates: int = 0):
+        """Overwrite the average's arena and its update counter (checkpoint restore; the average must be on)."""
+        a = np.ascontiguousarray(arena, dtype=np.float32)
+        assert a.size == self.arena_elems
+        torch.cuda.current_stream(self.device).synchronize()
+        _lib.check(self.lib.capgen_set_ema_state(self.h, a.ctypes.data_as(C.c_void_p), self.arena_elems,
+                                                 int(n_updates)))
+
+    def swap_ema(self):
+        """Exchange the parameters and the average in place (capgen_ema_swap): forward, losses, scoring
+        and every decoder then run on the averaged weights, and every updating call raises until the
+        next swap_ema()."""
+        torch.cuda.current_stream(self.device).synchronize()
+        _lib.check(self.lib.capgen_ema_swap(self.h))
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """with engine.averaged(): ... -- the averaged weights swapped in for the block, and back out
+        after it, exceptions included."""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
 
     def adam_step_count(self) -> int:
         """The number of Adam updates so far (the optimizer's step counter t; follows set_adam_state).
@@ -214,6 +286,15 @@ class Engine:
         _lib.check(self.lib.capgen_get_adam_state(self.h, C.byref(step), m.ctypes.data_as(C.c_void_p),
                                                   v.ctypes.data_as(C.c_void_p), self.arena_elems))
         return step.value, self._unpack(m), self._unpack(v)
+
+    def adam_arenas(self, exp_avg: np.ndarray, exp_avg_sq: np.ndarray) -> int:
+        """Fill two host f32 arrays of arena size with the moment arenas; returns the step counter."""
+        step = C.c_int64(0)
+        assert exp_avg.size == exp_avg_sq.size == self.arena_elems
+        torch.cuda.current_stream(self.device).synchronize()
+        _lib.check(self.lib.capgen_get_adam_state(self.h, C.byref(step), exp_avg.ctypes.data_as(C.c_void_p),
+                                                  exp_avg_sq.ctypes.data_as(C.c_void_p), self.arena_elems))
+        return step.value
 
     # ---- inputs ----------------------------------------------------------------------
     def _inputs(self, feats, pos, caps=None):

@@ -152,9 +152,14 @@ class MODEL_init:
     def decode_captions(self, caption_vector):
         return decode_captions(caption_vector, self.idx_to_word)
 
-    def set_schedule(self, lr_schedule=None, grad_clip=None):
-        """Replace the constructor's lr_schedule / grad_clip (capgen.train.train forwards its own here)."""
-        self._sched = ScheduledSteps(self.model.engine, lr_schedule, grad_clip)
+    def set_schedule(self, lr_schedule=None, grad_clip=None, weight_decay=None, ema_decay=None):
+        """Replace the constructor's lr_schedule / grad_clip / weight_decay / ema_decay (capgen.train.train
+        forwards its own here)."""
+        self._sched = ScheduledSteps(self.model.engine, lr_schedule, grad_clip, weight_decay, ema_decay)
+
+    def averaged(self):
+        """with model.averaged(): ... -- evaluate and decode on the averaged weights (Engine.averaged)."""
+        return self.model.engine.averaged()
 
     def save(self, path):
         torch.save(self.model.state_dict(), path)
@@ -164,21 +169,81 @@ class MODEL_init:
         self.model.load_state_dict(sd)
         self.model.eval()
 
+    def save_checkpoint(self, path):
+        """Everything a stopped run needs to go on, as one torch.save dict that loads with
+        weights_only=True: 'format'; 'model', the reference-keyed state dict (what save() writes, loadable
+        by the reference); 'adam' = {step, exp_avg, exp_avg_sq}; 'ema' = None or {decay, n_updates,
+        params}; 'lr'; 'grad_clip'; 'weight_decay'.  At world > 1 this first calls dp_sync_adam_state,
+        a COLLECTIVE: every rank must call save_checkpoint (any one of them may keep the file).  The
+        dropout seed is not part of the checkpoint (the engine has no getter for it): a resumed run
+        draws other masks than the uninterrupted one."""
+        eng = self.model.engine
+        if eng.dp_comm_info()[0] > 1:
+            eng.dp_sync_adam_state()
+        torch.save(checkpoint_dict(eng), path)
+
+    def load_checkpoint(self, path):
+        """Restore what save_checkpoint wrote: weights, Adam state, the average, learning rate, clip bound
+        and weight decay.  The trainer's lr_schedule / ema_decay schedules then continue from the restored
+        counters (they are re-read at the next step).  The train / eval state is left as it is."""
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+        if ck.get("format") != CHECKPOINT_FORMAT:
+            raise ValueError(f"capgen: {path} is not a {CHECKPOINT_FORMAT} checkpoint")
+        eng = self.model.engine
+        self.model.load_state_dict(ck["model"])
+        ad = ck["adam"]
+        eng.set_adam_state(int(ad["step"]), ad["exp_avg"].numpy(), ad["exp_avg_sq"].numpy())
+        eng.set_lr(float(ck["lr"]))
+        eng.set_grad_clip(ck["grad_clip"])
+        eng.set_weight_decay(ck["weight_decay"])
+        if ck["ema"] is None:
+            eng.set_ema(None)
+        else:
+            eng.set_ema(float(ck["ema"]["decay"]))
+            eng.set_ema_arena(ck["ema"]["params"].numpy(), int(ck["ema"]["n_updates"]))
+        sched = getattr(self, "_sched", None)
+        if sched is not None:
+            sched._done = sched._ema_done = None
+
+
+CHECKPOINT_FORMAT = "capgen-checkpoint-1"
+
+
+def checkpoint_dict(eng):
+    """The checkpoint of MODEL_init.save_checkpoint from an engine (tensors, numbers, None: nothing
+    that torch.load(weights_only=True) refuses)."""
+    decay, n_updates, swapped = eng.ema_info()
+    if swapped:
+        raise RuntimeError("capgen: save_checkpoint inside averaged(): the parameters hold the average")
+    m = np.empty(eng.arena_elems, np.float32)
+    v = np.empty(eng.arena_elems, np.float32)
+    step = eng.adam_arenas(m, v)
+    ema = None
+    if decay != 0.0:
+        ema = {"decay": float(decay), "n_updates": int(n_updates), "params": torch.from_numpy(eng.ema_arena())}
+    return {"format": CHECKPOINT_FORMAT, "model": eng.state_dict(),
+            "adam": {"step": int(step), "exp_avg": torch.from_numpy(m), "exp_avg_sq": torch.from_numpy(v)},
+            "ema": ema, "lr": float(eng.lr), "grad_clip": eng.grad_clip, "weight_decay": eng.weight_decay}
+
 
 class TRANSFORMER(MODEL_init):
     """grad_clip: clip every update's gradients to this global L2 norm (torch's clip_grad_norm_;
     float('inf') only measures, engine.grad_norm()); lr_schedule: a callable t -> learning rate
     (capgen.schedule), applied before each train step with t the Adam step number of that update.
-    None (default) for both: the engine is never told anything."""
+    weight_decay: decoupled decay as torch.optim.AdamW (Engine.set_weight_decay).  ema_decay: keep an
+    exponential moving average of the weights (Engine.set_ema; evaluate on it inside averaged()) -- a
+    float, or a callable of the average's update count such as capgen.schedule.ema_warmup(0.999).
+    None (default) for all four: the engine is never told anything."""
 
     def __init__(self, config: CapgenConfig | None = None, word_to_idx=None, word_to_idx_path=None,
-                 device="cuda:0", state_dict=None, grad_clip=None, lr_schedule=None):
+                 device="cuda:0", state_dict=None, grad_clip=None, lr_schedule=None, weight_decay=None,
+                 ema_decay=None):
         super().__init__(word_to_idx, word_to_idx_path)
         cfg = (config or CapgenConfig()).replace(num_vocab=self.num_vocab)
         self.config = cfg
         self.device = torch.device(device)
         self.model = Transformer.from_config(cfg, self.device, state_dict=state_dict)
-        self._sched = ScheduledSteps(self.model.engine, lr_schedule, grad_clip)
+        self._sched = ScheduledSteps(self.model.engine, lr_schedule, grad_clip, weight_decay, ema_decay)
         self._stage = {}
         self._host_stager = None
 
@@ -240,7 +305,7 @@ class SelfCriticNetwork(MODEL_init):
     def __init__(self, config: CapgenConfig | None = None, word_to_idx=None, word_to_idx_path=None,
                  device="cuda:0", state_dict=None, structure_loss_weight=0.5, cider_reward_weight=1.0,
                  bleu_reward_weight=1.0, entropy_reward_weight=1.0, self_cider_reward_weight=1.0, df="corpus",
-                 grad_clip=None, lr_schedule=None):
+                 grad_clip=None, lr_schedule=None, weight_decay=None, ema_decay=None):
         super().__init__(word_to_idx, word_to_idx_path)
         from .scst import RewardScorer
         cfg = (config or CapgenConfig()).replace(num_vocab=self.num_vocab)
@@ -248,7 +313,7 @@ class SelfCriticNetwork(MODEL_init):
         self.device = torch.device(device)
         # PolicyNetwork (model_RL.py): generate_caption then decodes with LogSoftmax scoring
         self.model = PolicyNetwork.from_config(cfg, self.device, state_dict=state_dict)
-        self._sched = ScheduledSteps(self.model.engine, lr_schedule, grad_clip)  # (as TRANSFORMER's)
+        self._sched = ScheduledSteps(self.model.engine, lr_schedule, grad_clip, weight_decay, ema_decay)  # (as TRANSFORMER's)
         if isinstance(df, str) and df == "corpus":
             import warnings
             warnings.warn("capgen SelfCriticNetwork: CIDEr-D document frequencies from the scored references "
@@ -302,7 +367,7 @@ class RolloutSelfCritic(MODEL_init):
     def __init__(self, config: CapgenConfig | None = None, word_to_idx=None, word_to_idx_path=None,
                  device="cuda:0", state_dict=None, n_samples=5, temperature=1.0, top_k=0, baseline="greedy",
                  cider_reward_weight=1.0, bleu_reward_weight=0.0, df="corpus", reward_fn=None, seed=None,
-                 grad_clip=None, lr_schedule=None, top_p=1.0):
+                 grad_clip=None, lr_schedule=None, top_p=1.0, weight_decay=None, ema_decay=None):
         super().__init__(word_to_idx, word_to_idx_path)
         from .scst import RewardScorer
         if baseline not in ("greedy", "mean"):
@@ -313,7 +378,7 @@ class RolloutSelfCritic(MODEL_init):
         self.config = cfg
         self.device = torch.device(device)
         self.model = PolicyNetwork.from_config(cfg, self.device, state_dict=state_dict)
-        self._sched = ScheduledSteps(self.model.engine, lr_schedule, grad_clip)  # (as TRANSFORMER's)
+        self._sched = ScheduledSteps(self.model.engine, lr_schedule, grad_clip, weight_decay, ema_decay)  # (as TRANSFORMER's)
         self.n_samples, self.temperature, self.top_k = int(n_samples), float(temperature), int(top_k)
         self.top_p = float(top_p)
         self.baseline, self.reward_fn, self.seed = baseline, reward_fn, seed

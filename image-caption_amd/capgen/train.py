@@ -18,6 +18,7 @@ TensorBoard writer / COCO evaluation (un-vendored coco-caption) are caller hooks
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import pickle
 
@@ -33,16 +34,36 @@ def _gather(store, idx):
 
 def train(model, train_split, valid_split, num_epoch, batch_size, output_path, target_dir=None,
           eval_every=100, sample_every=2500, write_log=("loss",), evaluate=None, log=print,
-          device="cuda:0", feature_dtype=torch.bfloat16, seed=0, grad_clip=None, lr_schedule=None):
+          device="cuda:0", feature_dtype=torch.bfloat16, seed=0, grad_clip=None, lr_schedule=None,
+          weight_decay=None, ema_decay=None, eval_averaged=False, resume=None):
     """train_split / valid_split: dicts as returned by capgen.data.load_split (features,
     positions, captions, image_idxs).  Returns the per-epoch score dicts.
 
     grad_clip / lr_schedule (both None by default: nothing changes): handed to the model
     (`model.set_schedule`, the trainers' constructor arguments of the same names).  With clipping or
     measuring on and "grad_norm" in write_log, the step log also carries the last update's global
-    gradient norm (before clipping)."""
-    if grad_clip is not None or lr_schedule is not None:
+    gradient norm (before clipping).
+
+    weight_decay / ema_decay (None by default, handed to the model in the same way): AdamW's decoupled
+    decay and an averaged copy of the weights.  resume: a checkpoint_{epoch}.pt of an earlier run, loaded
+    (`model.load_checkpoint`) before the first step, after the options above are set.  eval_averaged: the
+    per-epoch evaluation (losses and greedy captions) runs inside `model.averaged()`, and the averaged
+    weights are also written as model_{epoch}.ema.pt.  With any of these four set, checkpoint_{epoch}.pt
+    (`model.save_checkpoint`) is written beside model_{epoch}.pt.  With the defaults nothing changes."""
+    new_options = weight_decay is not None or ema_decay is not None or eval_averaged or resume is not None
+    if weight_decay is not None or ema_decay is not None:
+        model.set_schedule(lr_schedule=lr_schedule, grad_clip=grad_clip, weight_decay=weight_decay,
+                           ema_decay=ema_decay)
+    elif grad_clip is not None or lr_schedule is not None:
         model.set_schedule(lr_schedule=lr_schedule, grad_clip=grad_clip)
+    if resume is not None:
+        model.load_checkpoint(resume)
+    if eval_averaged and ema_decay is None:
+        # (a stand-in model without an engine cannot be asked; a real one fails here, not after an epoch)
+        eng = getattr(getattr(model, "model", None), "engine", None)
+        if eng is not None and eng.ema_info()[0] == 0.0:
+            raise ValueError("capgen train: eval_averaged needs an average -- pass ema_decay, or resume from a "
+                             "checkpoint that holds one")
     log_norm = "grad_norm" in write_log
     write_log = tuple(k for k in write_log if k != "grad_norm")  # (not a compute_loss key)
     model_dir = os.path.join(output_path, "model")
@@ -91,16 +112,19 @@ def train(model, train_split, valid_split, num_epoch, batch_size, output_path, t
         # evaluation (main.py:104-146)
         valid_caption = [""] * n_valid_images
         logs = {k: {"train": 0.0, "valid": 0.0} for k in write_log}
-        for (t_idx, t_caps), (v_idx, v_caps) in zip(loaders["train"], loaders["valid"]):
-            tl = loss_of("train", t_idx, t_caps)
-            vl = loss_of("valid", v_idx, v_caps)
-            for k in write_log:
-                logs[k]["train"] += tl[k].mean().item()
-                logs[k]["valid"] += vl[k].mean().item()
-            f, p = _gather(stores["valid"], v_idx)
-            captions, _ = model.generate_caption(object_features=f, position_features=p)
-            for j, c in zip(v_idx.tolist(), captions):
-                valid_caption[j] = c
+        with model.averaged() if eval_averaged else contextlib.nullcontext():
+            for (t_idx, t_caps), (v_idx, v_caps) in zip(loaders["train"], loaders["valid"]):
+                tl = loss_of("train", t_idx, t_caps)
+                vl = loss_of("valid", v_idx, v_caps)
+                for k in write_log:
+                    logs[k]["train"] += tl[k].mean().item()
+                    logs[k]["valid"] += vl[k].mean().item()
+                f, p = _gather(stores["valid"], v_idx)
+                captions, _ = model.generate_caption(object_features=f, position_features=p)
+                for j, c in zip(v_idx.tolist(), captions):
+                    valid_caption[j] = c
+            if eval_averaged:  # (save() writes the parameter arena: the average, in here)
+                model.save(path=os.path.join(model_dir, f"model_{epoch}.ema.pt"))
         # the reference divides by len(valid_dataloader) (main.py:130-132)
         for k in write_log:
             logs[k]["train"] /= max(1, len(loaders["valid"]))
@@ -112,5 +136,7 @@ def train(model, train_split, valid_split, num_epoch, batch_size, output_path, t
         log({"epoch": epoch, "train_loss": scores["loss"]["train"] if "loss" in scores else None,
              "valid_loss": scores["loss"]["valid"] if "loss" in scores else None})
         model.save(path=os.path.join(model_dir, f"model_{epoch}.pt"))
+        if new_options:
+            model.save_checkpoint(os.path.join(model_dir, f"checkpoint_{epoch}.pt"))
         history.append(scores)
     return history

@@ -68,6 +68,7 @@ int capgen_set_params(capgen_t* h, const float* src, int64_t n) {
   return guarded([&] {
     set_device(h);
     require(n == h->L.total, "set_params: size mismatch");
+    h->require_unswapped("set_params");
     hz::host_sync(h->es);
     CAPGEN_HIP(hipMemcpy(h->params, src, n * 4, hipMemcpyHostToDevice));
     h->refresh_shadow(h->es);
@@ -112,6 +113,7 @@ int capgen_set_adam_state(capgen_t* h, int64_t step, const float* m, const float
   return guarded([&] {
     set_device(h);
     require(n == h->L.total, "set_adam_state: size mismatch");
+    h->require_unswapped("set_adam_state");
     hz::host_sync(h->es);
     CAPGEN_HIP(hipMemcpy(h->step, &step, 8, hipMemcpyHostToDevice));
     if (m) CAPGEN_HIP(hipMemcpy(h->am, m, n * 4, hipMemcpyHostToDevice));
@@ -183,6 +185,60 @@ int capgen_set_grad_clip(capgen_t* h, float max_norm) {
   });
 }
 
+int capgen_set_weight_decay(capgen_t* h, float wd) {
+  return guarded([&] {
+    set_device(h);
+    require(std::isfinite(wd) && wd >= 0.f, "set_weight_decay: wd must be finite and >= 0 (0 = off)");
+    h->set_weight_decay(wd);
+  });
+}
+
+int capgen_set_ema(capgen_t* h, float decay) {
+  return guarded([&] {
+    set_device(h);
+    require(decay == 0.f || (decay > 0.f && decay < 1.f), "set_ema: decay must be 0 (off) or in (0, 1)");  // (NaN fails too)
+    h->set_ema(decay);
+  });
+}
+
+int capgen_ema_info(capgen_t* h, float* decay, int64_t* n_updates, int* swapped) {
+  return guarded([&] {
+    require(h != nullptr, "null engine handle");
+    if (decay) *decay = h->ema_decay;
+    if (n_updates) *n_updates = h->ema_updates;
+    if (swapped) *swapped = h->ema_swapped ? 1 : 0;
+  });
+}
+
+int capgen_get_ema(capgen_t* h, float* dst, int64_t n) {
+  return guarded([&] {
+    set_device(h);
+    require(n == h->L.total, "get_ema: size mismatch");
+    require(h->ema != nullptr, "get_ema: the average was never enabled (capgen_set_ema)");
+    hz::host_sync(h->es);
+    hz::host_sync(h->ec);
+    CAPGEN_HIP(hipMemcpy(dst, h->ema, n * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int capgen_set_ema_state(capgen_t* h, const float* src, int64_t n, int64_t n_updates) {
+  return guarded([&] {
+    set_device(h);
+    require(n == h->L.total, "set_ema_state: size mismatch");
+    require(src != nullptr && n_updates >= 0, "set_ema_state: null source or negative n_updates");
+    require(h->ema_on(), "set_ema_state: the average is off (capgen_set_ema first)");
+    h->require_unswapped("set_ema_state");
+    h->set_ema_state(src, n_updates);
+  });
+}
+
+int capgen_ema_swap(capgen_t* h) {
+  return guarded([&] {
+    set_device(h);
+    h->ema_swap();
+  });
+}
+
 int capgen_last_grad_norm(capgen_t* h, float* host_out) {
   return guarded([&] {
     set_device(h);
@@ -218,6 +274,7 @@ int capgen_adam_step(capgen_t* h, void* stream) {
   return guarded([&] {
     set_device(h);
     hipStream_t cs = (hipStream_t)stream;
+    h->require_unswapped("adam_step");
     h->enter(cs);
     h->adam(h->es);
     h->leave(cs);
@@ -228,6 +285,7 @@ int capgen_train_step(capgen_t* h, const void* feats, int ft, const float* pos, 
                       int T, float* loss_out, void* stream) {
   return guarded([&] {
     set_device(h);
+    h->require_unswapped("train_step");
     h->train_step(feats, dt(ft), pos, caps, B, N, T, loss_out, (hipStream_t)stream);
     h->dp_check((hipStream_t)stream, loss_out);
   });
@@ -293,6 +351,7 @@ int capgen_train_step_indexed(capgen_t* h, const void* feat_store, int feats_dty
   return guarded([&] {
     set_device(h);
     require(n_images >= 1, "train_step_indexed: empty store");
+    h->require_unswapped("train_step_indexed");
     {
       Scoped<StepIn> inputs(h->in, StepIn{img_idx, n_images, nullptr});
       h->train_step(feat_store, dt(feats_dtype), pos_store, caps, B, N, T, loss_out, (hipStream_t)stream);
@@ -309,6 +368,7 @@ int capgen_train_step_weighted(capgen_t* h, const void* feats, int feats_dtype, 
     require(weights != nullptr, "train_step_weighted: weights is null");
     require(!h->cfg.focal_loss, "train_step_weighted: focal_loss transforms an unweighted mean");
     require(!img_idx || n_images >= 1, "train_step_weighted: empty store");
+    if (train) h->require_unswapped("train_step_weighted");
     hipStream_t cs = (hipStream_t)stream;
     const DType ft = dt(feats_dtype);
     Scoped<StepIn> inputs(h->in, StepIn{img_idx, img_idx ? n_images : 0, weights});
@@ -354,6 +414,7 @@ int capgen_rl_finish(capgen_t* h, const float* scores, float structure_loss_weig
                      void* stream) {
   return guarded([&] {
     set_device(h);
+    if (train) h->require_unswapped("rl_finish");
     h->rl_finish(scores, structure_loss_weight, loss_out, train != 0, (hipStream_t)stream);
   });
 }
@@ -430,6 +491,7 @@ int capgen_dp_init(capgen_t* h, const char id[128], int rank, int world) {
   return guarded([&] {
     set_device(h);
     require(world >= 1 && rank >= 0 && rank < world, "dp_init: bad rank/world");
+    h->require_unswapped("dp_init");
     h->dp_init(id, rank, world);
   });
 }

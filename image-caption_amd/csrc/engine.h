@@ -241,6 +241,16 @@ struct capgen_engine {
   float lr_cur = 0.f;
   float clip_cur = 0.f;  // 0: clipping off (the default schedule); > 0 clips, +inf measures only
   bool norm_valid = false;  // opt[2] holds the norm of an update issued with clip_on()
+  // decoupled weight decay and the averaged weights (capgen_set_weight_decay / capgen_set_ema), both off
+  // by default.  Two more device words beside the four above, set through set_opt_word like them:
+  // opt[4] = wd (the Adam prep derives adam_scal[2] = 1 - lr * wd from it), opt[5] = 1 - decay (read by
+  // the update kernel).  ema: the average's arena, L.total f32, allocated at the first enable.
+  static constexpr int kOptWd = 4, kOptEmaRate = 5;
+  float wd_cur = 0.f;
+  float* ema = nullptr;
+  float ema_decay = 0.f;     // 0: off
+  int64_t ema_updates = 0;   // updates issued while on (a graph replay counts, its capture does not)
+  bool ema_swapped = false;  // params holds the average and ema the raw weights (ema_swap)
   // the norm's partial sums: gn_part[gn_slots_cap] doubles, one slot per sum-of-squares workgroup, filled
   // in issue order within a step (gn_slots: used so far), and the step's total (all-reduced under DP)
   double* gn_part = nullptr;
@@ -302,6 +312,10 @@ struct capgen_engine {
   // rank's chunks only until capgen_dp_sync_adam_state (resp. the next backward) -- the whole-arena getters
   // refuse them in between instead of returning stale data
   bool moments_sharded = false, grads_sharded = false;
+  bool ema_sharded = false;  // the same for the average (updated while on by a sharded step)
+  // what the captured whole-step graph's host code set of the two flags above: a replay runs no host
+  // code, so train_step sets them (and ema_sharded) again where it launches the graph
+  bool gexec_moments_sharded = false, gexec_grads_sharded = false;
   std::vector<std::array<int64_t, 2>> zbuckets;  // this step's bucket ranges, in issue order
   bool zbuckets_checked = false;
   bool dp_checked = false;  // dp_check has run
@@ -454,6 +468,18 @@ struct capgen_engine {
     return it == dtile.end() || !dtiles ? nullptr : dtiles + it->second;
   }
   bool clip_on() const { return clip_cur != 0.f; }
+  bool wd_on() const { return wd_cur != 0.f; }
+  bool ema_on() const { return ema_decay != 0.f; }
+  // the optional parts of an update of the arena range starting at off (none by default)
+  AdamOpt adam_opt(int64_t off) const {
+    return {wd_on() ? adam_scal + 2 : nullptr, ema_on() ? ema + off : nullptr, opt + kOptEmaRate};
+  }
+  const float* wd_word() const { return wd_on() ? opt + kOptWd : nullptr; }
+  // the calls that update parameters refuse to run on the averaged weights
+  void require_unswapped(const char* what) const {
+    require(!ema_swapped, std::string(what) + ": the averaged weights are swapped into the parameters; call "
+                                              "capgen_ema_swap to swap them back first");
+  }
   bool tuned(int B, int N, int T) const {
     for (auto& t : tuned_shapes)
       if (t[0] == B && t[1] == N && t[2] == T) return true;
@@ -851,6 +877,12 @@ struct capgen_engine {
   void dp_check(hipStream_t cs, const float* loss, bool force = false);
   void set_lr(float lr);
   void set_grad_clip(float max_norm);
+  void drop_step_graph();
+  void count_update(hipStream_t s);
+  void set_weight_decay(float wd);
+  void set_ema(float decay);
+  void set_ema_state(const float* host_src, int64_t n_updates);
+  void ema_swap();
   void dp_init(const char id[128], int rank_, int world_);
   void dp_sync_adam_state();
   void dp_set_global_count(float count);

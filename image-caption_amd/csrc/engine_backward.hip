@@ -143,7 +143,8 @@ void capgen_engine::backward(hipStream_t s, bool step_params) {
     // through the buckets' events)
     hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
     CAPGEN_HIP(hipStreamIsCapturing(s, &cst));
-    adam_prepare(step, opt, cfg.beta1, cfg.beta2, adam_scal, cst == hipStreamCaptureStatusNone ? ec : s);
+    adam_prepare(step, opt, cfg.beta1, cfg.beta2, adam_scal, cst == hipStreamCaptureStatusNone ? ec : s, wd_word());
+    if (ema_on() && cst == hipStreamCaptureStatusNone) ++ema_updates;  // (a replay is counted where it launches)
     zbuckets.clear();
     gn_deferred.clear();
     gn_slots = 0;

@@ -114,12 +114,21 @@ void capgen_engine::train_step(const void* f, DType ft, const float* pos, const 
     if (!(gexec && gkey == k)) {
       drop_graph();
       tune_once(f, ft, pos, caps, B, N, T, loss);
+      const bool moments_were = moments_sharded;
+      moments_sharded = false;
       gexec = capture(es, [&] { halves(es, eager_fwd, "forward enqueue"); });
       gkey = k;
+      gexec_moments_sharded = moments_sharded, gexec_grads_sharded = grads_sharded;
+      moments_sharded = moments_sharded || moments_were;
     }
     // the replay runs the captured Adam and re-cast of the shadow with no host code: the weight
     // version must move with it, or the decode tiles (build_dtiles) would keep the old weights
     ++wver;
+    if (ema_on()) ++ema_updates;  // (the capture's host code counted nothing)
+    // a sharded step leaves the moments, the average and the gradient arena current in this rank's
+    // chunks only, replayed or not (after capgen_dp_sync_adam_state, or an eager backward, as well)
+    if (gexec_moments_sharded) moments_sharded = true, ema_sharded = ema_sharded || ema_on();
+    grads_sharded = gexec_grads_sharded;
     CAPGEN_HIP(hipGraphLaunch(gexec, es));
   }
   leave(cs);
@@ -260,7 +269,7 @@ capgen_engine::~capgen_engine() {
     if (p) (void)hipFree(p);
   if (count_host) (void)hipHostFree(count_host);
   if (opt_host) (void)hipHostFree(opt_host);
-  for (void* p : {(void*)opt, (void*)gn_part, (void*)gn_sum})
+  for (void* p : {(void*)opt, (void*)gn_part, (void*)gn_sum, (void*)ema})
     if (p) (void)hipFree(p);
   if (ev_opt) (void)hipEventDestroy(ev_opt);
   if (dp_chk) (void)hipFree(dp_chk);

@@ -60,7 +60,8 @@ void capgen_engine::adam_range(int64_t off, int64_t n, hipStream_t s, int grid_c
       at.dst[at.n++] = wtile + kv.second.first;
     }
   adam_update(params + off, grads + off, am + off, av + off, (size_t)n, cfg.beta1, cfg.beta2, cfg.eps, adam_scal,
-              ns > 0 ? shadow + off : nullptr, (size_t)ns, s, grid_cap, fused_tiles ? at : AdamTiles{}, gscale);
+              ns > 0 ? shadow + off : nullptr, (size_t)ns, s, grid_cap, fused_tiles ? at : AdamTiles{}, gscale,
+              adam_opt(off));
   if (ns > 0) retile(off, ns, s, /*trans_only=*/fused_tiles);  // (the transposed ones: always a launch)
 }
 
@@ -102,6 +103,7 @@ void capgen_engine::bucket_reduce(int64_t off, int64_t n) {
   if (sharded) {
     const int64_t c = n / zw, o = off + (int64_t)zrank() * c;
     if (zw > 1) moments_sharded = true;  // this rank's moments are current in its chunks only
+    if (zw > 1 && ema_on()) ema_sharded = true;  // ... and so is its average
     if (comm && zw > 1) grads_sharded = true;  // the gradient arena holds reduce-scattered chunks
     // in place: rank r's chunk of the summed gradients lands at grads + o
     if (comm) {
@@ -128,7 +130,7 @@ void capgen_engine::bucket_adam(int64_t off, int64_t n, int grid_cap, const floa
     const int64_t c = n / zw, o = off + (int64_t)zrank() * c;
     const int64_t ns = shadow ? std::max<int64_t>(0, std::min(n, L.n_dense - off)) : 0;
     adam_update(params + o, grads + o, am + o, av + o, (size_t)c, cfg.beta1, cfg.beta2, cfg.eps, adam_scal, nullptr, 0,
-                ec, grid_cap, AdamTiles{}, gscale);
+                ec, grid_cap, AdamTiles{}, gscale, adam_opt(o));
     // in place: every rank's updated chunk -> params + off (sendbuff = recvbuff + rank * c)
     if (comm) {
       nccl_op(ec, "all_gather", params + off, n * 4);
@@ -181,7 +183,8 @@ void capgen_engine::allreduce_grads(hipStream_t s) {
 
 void capgen_engine::adam(hipStream_t s) {
   ++wver;
-  adam_prepare(step, opt, cfg.beta1, cfg.beta2, adam_scal, s);
+  adam_prepare(step, opt, cfg.beta1, cfg.beta2, adam_scal, s, wd_word());
+  count_update(s);
   // clipping on: the norm of the whole arena (the gradients are whole and, under DP, already
   // all-reduced on every rank: no collective), then Adam with the scale
   const float* gscale = nullptr;
@@ -192,7 +195,7 @@ void capgen_engine::adam(hipStream_t s) {
     norm_valid = true;
   }
   adam_update(params, grads, am, av, (size_t)L.total, cfg.beta1, cfg.beta2, cfg.eps, adam_scal, shadow,
-              shadow ? (size_t)L.n_dense : 0, s, 0, AdamTiles{}, gscale);
+              shadow ? (size_t)L.n_dense : 0, s, 0, AdamTiles{}, gscale, adam_opt(0));
   if (shadow) retile(0, L.n_dense, s);
 }
 
@@ -239,15 +242,79 @@ void capgen_engine::set_lr(float lr) {
   lr_cur = lr;
 }
 
+// the whole-step graph holds the update's schedule and kernel variants; the forward graph does not
+void capgen_engine::drop_step_graph() {
+  if (!gexec) return;
+  (void)hipGraphExecDestroy(gexec);
+  gexec = nullptr;
+}
+
 void capgen_engine::set_grad_clip(float max_norm) {
   const bool on = max_norm != 0.f;
-  // the whole-step graph holds the schedule (norm pass, deferred Adam); the forward graph does not
-  if (on != clip_on() && gexec) {
-    (void)hipGraphExecDestroy(gexec);
-    gexec = nullptr;
-  }
+  if (on != clip_on()) drop_step_graph();  // (norm pass, deferred Adam)
   if (on) set_opt_word(1, max_norm);
   clip_cur = max_norm;
+}
+
+// one parameter update is being issued on s (not: captured -- the replays are counted where they launch)
+void capgen_engine::count_update(hipStream_t s) {
+  if (!ema_on()) return;
+  hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+  CAPGEN_HIP(hipStreamIsCapturing(s, &cst));
+  if (cst == hipStreamCaptureStatusNone) ++ema_updates;
+}
+
+// on <-> off changes the prepare kernel and the update's variant: the step graph is re-captured; a new
+// value while on is one device word, read by the replay
+void capgen_engine::set_weight_decay(float wd) {
+  if ((wd != 0.f) != wd_on()) drop_step_graph();
+  if (wd != 0.f) set_opt_word(kOptWd, wd);
+  wd_cur = wd;
+}
+
+void capgen_engine::set_ema(float decay) {
+  const bool on = decay != 0.f;
+  if (on != ema_on()) {
+    // (swapped: the parameter arena holds the average -- neither a copy of it nor a stop would mean anything)
+    require(!ema_swapped, "set_ema: the averaged weights are swapped in (capgen_ema_swap): only the decay of an "
+                          "enabled average may change until they are swapped back");
+    drop_step_graph();
+  }
+  if (on && !ema_on()) {  // off -> on: the average starts as a copy of the parameters
+    hz::host_sync(es);
+    hz::host_sync(ec);
+    if (!ema) CAPGEN_HIP(hipMalloc(&ema, (size_t)L.total * 4));
+    CAPGEN_HIP(hipMemcpyAsync(ema, params, (size_t)L.total * 4, hipMemcpyDeviceToDevice, es));
+    hz::host_sync(es);
+    ema_updates = 0;
+    ema_sharded = false;
+  }
+  if (on) set_opt_word(kOptEmaRate, (float)(1.0 - (double)decay));
+  ema_decay = decay;
+}
+
+void capgen_engine::set_ema_state(const float* host_src, int64_t n_updates) {
+  hz::host_sync(es);
+  hz::host_sync(ec);
+  CAPGEN_HIP(hipMemcpy(ema, host_src, (size_t)L.total * 4, hipMemcpyHostToDevice));
+  hz::host_sync(nullptr);
+  ema_updates = n_updates;
+  ema_sharded = false;
+}
+
+// params <-> ema in place: no pointer moves, so the cached graphs stay valid; the bf16 shadow and the
+// tiles follow (the decode tiles and the bf16 embedding copy through the weight version)
+void capgen_engine::ema_swap() {
+  require(ema_on() && ema, "ema_swap: the average is off (capgen_set_ema)");
+  require(!(ema_sharded && zworld() > 1), "ema_swap: after sharded (ZeRO-1) steps this rank's average is current in "
+                                          "its own chunks only: call capgen_dp_sync_adam_state on every rank first");
+  hz::host_sync(es);
+  hz::host_sync(ec);
+  arena_swap(params, ema, (size_t)L.total, es);
+  refresh_shadow(es);
+  ++wver;  // (an fp32 engine has no shadow to re-tile: its weights moved all the same)
+  hz::host_sync(es);
+  ema_swapped = !ema_swapped;
 }
 
 // join the communicator as rank of world, and replicate rank 0's parameters
@@ -259,6 +326,13 @@ void capgen_engine::dp_init(const char id[128], int rank_, int world_) {
   rank = rank_, world = world_;
   drop_graph();
   NCCL_CHECK(ncclBroadcast(params, params, (size_t)L.total, ncclFloat, 0, comm, es));
+  // an average enabled before this call followed this rank's former weights: it restarts as a copy of
+  // the replicated ones, on every rank alike (as off -> on)
+  if (ema_on()) {
+    CAPGEN_HIP(hipMemcpyAsync(ema, params, (size_t)L.total * 4, hipMemcpyDeviceToDevice, es));
+    ema_updates = 0;
+    ema_sharded = false;
+  }
   refresh_shadow(es);
   hz::host_sync(es);
 }
@@ -274,8 +348,10 @@ void capgen_engine::dp_sync_adam_state() {
     const int64_t c = b[1] / zw, o = b[0] + (int64_t)zrank() * c;
     NCCL_CHECK(ncclAllGather(am + o, am + b[0], (size_t)c, ncclFloat, comm, es));
     NCCL_CHECK(ncclAllGather(av + o, av + b[0], (size_t)c, ncclFloat, comm, es));
+    if (ema_on()) NCCL_CHECK(ncclAllGather(ema + o, ema + b[0], (size_t)c, ncclFloat, comm, es));
   }
   moments_sharded = false;
+  if (ema_on()) ema_sharded = false;
   hz::host_sync(es);
 }
 

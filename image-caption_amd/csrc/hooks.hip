@@ -414,6 +414,38 @@ int capgen_debug_adam_scaled(float* p, const float* g, float* m, float* v, int64
   });
 }
 
+int capgen_debug_adam_ex(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
+                         float eps, int64_t* step, float* scal, void* shadow, int64_t n_shadow, int grid_cap,
+                         int n_tiles, const int64_t* tile_off, const int64_t* tile_len, void* const* tile_dst,
+                         const float* gscale, float weight_decay, float* ema, float ema_decay, void* stream) {
+  return guarded([&] {
+    const hipStream_t s = (hipStream_t)stream;
+    require(n >= 0 && n_shadow >= 0 && n_shadow <= n, "debug_adam_ex: 0 <= n_shadow <= n");
+    require(n % 4 == 0 && n_shadow % 4 == 0, "debug_adam_ex: n and n_shadow must be multiples of 4");
+    require(n_tiles >= 0 && n_tiles <= AdamTiles::kMax, "debug_adam_ex: at most AdamTiles::kMax tiled ranges");
+    require(std::isfinite(weight_decay) && weight_decay >= 0.f, "debug_adam_ex: weight_decay must be finite and >= 0");
+    require(!ema || (ema_decay > 0.f && ema_decay < 1.f), "debug_adam_ex: ema_decay must be in (0, 1)");
+    AdamTiles tiles;
+    tiles.n = n_tiles;
+    for (int t = 0; t < n_tiles; ++t)
+      tiles.off[t] = tile_off[t], tiles.len[t] = tile_len[t], tiles.dst[t] = reinterpret_cast<bf16*>(tile_dst[t]);
+    const float words[3] = {lr, weight_decay, (float)(1.0 - (double)ema_decay)};
+    CAPGEN_HIP(hipMemcpyAsync(scal + 4, words, sizeof words, hipMemcpyHostToDevice, s));
+    CAPGEN_HIP(hipStreamSynchronize(s));  // (the words leave this frame before it returns)
+    const bool decay = weight_decay != 0.f;
+    adam_prepare(step, scal + 4, b1, b2, scal, s, decay ? scal + 5 : nullptr);
+    adam_update(p, g, m, v, (size_t)n, b1, b2, eps, scal, reinterpret_cast<bf16*>(shadow), (size_t)n_shadow, s,
+                grid_cap, tiles, gscale, AdamOpt{decay ? scal + 2 : nullptr, ema, scal + 6});
+  });
+}
+
+int capgen_debug_arena_swap(float* a, float* b, int64_t n, int grid_cap, void* stream) {
+  return guarded([&] {
+    require(n >= 0, "debug_arena_swap: n must be >= 0");
+    arena_swap(a, b, (size_t)n, (hipStream_t)stream, grid_cap);
+  });
+}
+
 int capgen_debug_grad_norm(const float* g, int64_t n, float max_norm, int grid_cap, double* partials, int cap,
                            float* out2, void* stream) {
   return guarded([&] {

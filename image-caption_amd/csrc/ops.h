@@ -111,12 +111,25 @@ struct AdamTiles {
   int64_t len[kMax] = {};
   bf16* dst[kMax] = {};
 };
+// Optional parts of the update, each a device word so that a replayed graph reads new values.  decay: the
+// factor 1 - lr * wd (adam_prepare with wd writes it to scal[2]) every parameter is multiplied by before
+// its update (torch.optim.AdamW).  ema (n f32, beside p) with ema_rate = 1 - decay: the exponential
+// moving average e += (p_new - e) * rate of the updated parameters.
+struct AdamOpt {
+  const float* decay = nullptr;
+  float* ema = nullptr;
+  const float* ema_rate = nullptr;
+};
 // gscale (optional, one device float): every gradient is multiplied by *gscale before both moment updates
 void adam_update(float* p, const float* g, float* m, float* v, size_t n, float b1, float b2, float eps,
                  const float* scal, bf16* shadow, size_t n_shadow, hipStream_t s, int grid_cap = 0,
-                 const AdamTiles& tiles = AdamTiles{}, const float* gscale = nullptr);
-// the learning rate read from a device word (the same formula: an unchanged rate gives the same bits)
-void adam_prepare(int64_t* step, const float* lr, float b1, float b2, float* scal, hipStream_t s);
+                 const AdamTiles& tiles = AdamTiles{}, const float* gscale = nullptr, const AdamOpt& x = AdamOpt{});
+// the learning rate read from a device word (the same formula: an unchanged rate gives the same bits);
+// wd given (a device word): also scal[2] = (float)(1 - lr * wd), computed in double (else two floats)
+void adam_prepare(int64_t* step, const float* lr, float b1, float b2, float* scal, hipStream_t s,
+                  const float* wd = nullptr);
+// a[i] <-> b[i] over n f32 (n % 4 == 0, disjoint); grid_cap 0: 2048 workgroups at most
+void arena_swap(float* a, float* b, size_t n, hipStream_t s, int grid_cap = 0);
 // Global gradient norm (torch.nn.utils.clip_grad_norm_).  grad_sumsq: the sum of squares of g[0, n)
 // (16-byte aligned, n % 4 == 0) in double, one double per workgroup into partials[0, grid) by plain
 // stores (no atomics: the value depends on n and the grid only); returns grid = grad_sumsq_grid(n,

@@ -1012,10 +1012,25 @@ __global__ void adam_prep_dev_kernel(int64_t* step, const float* lr, float b1, f
   scal[0] = (float)(-(double)*lr / bc1);
   scal[1] = (float)sqrt(bc2);
 }
-void adam_prepare(int64_t* step, const float* lr, float b1, float b2, float* scal, hipStream_t s) {
+// ... and, for the decoupled weight decay (torch.optim.AdamW: p *= 1 - lr * wd before the step's Adam
+// update), scal[2] = that factor from the two device words: in double, rounded once
+__global__ void adam_prep_wd_kernel(int64_t* step, const float* lr, const float* wd, float b1, float b2, float* scal) {
+  const int64_t t = ++(*step);
+  const double bc1 = 1.0 - pow((double)b1, (double)t);
+  const double bc2 = 1.0 - pow((double)b2, (double)t);
+  scal[0] = (float)(-(double)*lr / bc1);
+  scal[1] = (float)sqrt(bc2);
+  scal[2] = (float)(1.0 - (double)*lr * (double)*wd);
+}
+void adam_prepare(int64_t* step, const float* lr, float b1, float b2, float* scal, hipStream_t s, const float* wd) {
   require(lr != nullptr, "adam_prepare: null learning-rate word");
-  if (hz::active()) hz::op(s, "adam_prepare", {hz::rd(lr, 4), hz::wr(step, 8), hz::wr(scal, 8)});
-  adam_prep_dev_kernel<<<1, 1, 0, s>>>(step, lr, b1, b2, scal);
+  if (wd) {
+    if (hz::active()) hz::op(s, "adam_prepare", {hz::rd(lr, 4), hz::rd(wd, 4), hz::wr(step, 8), hz::wr(scal, 12)});
+    adam_prep_wd_kernel<<<1, 1, 0, s>>>(step, lr, wd, b1, b2, scal);
+  } else {
+    if (hz::active()) hz::op(s, "adam_prepare", {hz::rd(lr, 4), hz::wr(step, 8), hz::wr(scal, 8)});
+    adam_prep_dev_kernel<<<1, 1, 0, s>>>(step, lr, b1, b2, scal);
+  }
   CAPGEN_HIP(hipGetLastError());
 }
 
@@ -1028,23 +1043,47 @@ void adam_prepare(int64_t* step, const float* lr, float b1, float b2, float* sca
 // iteration measured 3.1 TB/s, round 4).
 constexpr int ADAM_U = 4;
 typedef float adam_f4 __attribute__((ext_vector_type(4)));  // (the nontemporal builtins take clang vectors)
-// GScale empty: the kernel as it was (the same parameters, the same code).  GScale = const float*: every
+// Opt empty: the kernel as it was (the same parameters, the same code).  Opt holds const float*: every
 // gradient is multiplied by *gscale (the clip coefficient of grad_norm_finish) once, before both
-// moment updates.
-template <class... GScale>
+// moment updates.  AdamDecayArg: p *= *factor (the prepare kernel's 1 - lr * wd) before the update, as
+// torch.optim.AdamW.  AdamEmaArg: after the update e += (p_new - e) * *rate (rate = 1 - decay:
+// torch.optim.swa_utils.get_ema_multi_avg_fn, e.lerp_(p, 1 - decay)); e is one more stream of the
+// same kind (16-B non-temporal loads issued with the others, 38 B per parameter instead of 30).
+// The options are types of the pack in the order {gscale, decay, ema}: compile-time variants, and the
+// two instantiations without them keep their names and their code.
+struct AdamDecayArg {
+  const float* factor;
+};
+struct AdamEmaArg {
+  adam_f4* e;
+  const float* rate;
+};
+template <class T, class... Opt>
+constexpr bool adam_has = (std::is_same_v<T, Opt> || ...);
+template <class T, class First, class... Rest>
+__device__ __forceinline__ T adam_arg(First first, Rest... rest) {
+  if constexpr (std::is_same_v<T, First>) return first;
+  else return adam_arg<T>(rest...);
+}
+template <class... Opt>
 __global__ void __launch_bounds__(256) adam_kernel(adam_f4* __restrict__ p, const adam_f4* __restrict__ g,
                                                    adam_f4* __restrict__ m, adam_f4* __restrict__ v, size_t n4,
                                                    float b1, float b2, float eps, const float* __restrict__ scal,
                                                    bf16* __restrict__ shadow, size_t n_shadow, AdamTiles tiles,
-                                                   GScale... gscale) {
-  constexpr bool SCALED = sizeof...(GScale) > 0;
+                                                   Opt... opt) {
+  constexpr bool SCALED = adam_has<const float*, Opt...>, DECAY = adam_has<AdamDecayArg, Opt...>,
+                 EMA = adam_has<AdamEmaArg, Opt...>;
   const float neg_step = scal[0], bc2s = scal[1];
   float gs = 1.f;
-  if constexpr (SCALED) gs = *(gscale, ...);
+  if constexpr (SCALED) gs = *adam_arg<const float*>(opt...);
+  float keep = 1.f, rate = 0.f;
+  adam_f4* __restrict__ e = nullptr;
+  if constexpr (DECAY) keep = *adam_arg<AdamDecayArg>(opt...).factor;
+  if constexpr (EMA) e = adam_arg<AdamEmaArg>(opt...).e, rate = *adam_arg<AdamEmaArg>(opt...).rate;
   const float b1c = 1.f - b1, b2c = 1.f - b2;
   const size_t stride = (size_t)gridDim.x * 256 * ADAM_U;
   for (size_t base = blockIdx.x * (size_t)(256 * ADAM_U) + threadIdx.x; base < n4; base += stride) {
-    adam_f4 pp[ADAM_U], gg[ADAM_U], mm[ADAM_U], vv[ADAM_U];
+    adam_f4 pp[ADAM_U], gg[ADAM_U], mm[ADAM_U], vv[ADAM_U], ee[EMA ? ADAM_U : 1];
 #pragma unroll
     for (int u = 0; u < ADAM_U; ++u) {
       // (a lane past the end re-reads element base: in range, its results are not stored)
@@ -1053,11 +1092,16 @@ __global__ void __launch_bounds__(256) adam_kernel(adam_f4* __restrict__ p, cons
       gg[u] = __builtin_nontemporal_load(g + i);
       mm[u] = __builtin_nontemporal_load(m + i);
       vv[u] = __builtin_nontemporal_load(v + i);
+      if constexpr (EMA) ee[u] = __builtin_nontemporal_load(e + i);
     }
     // every load above is issued before the first value is consumed (hipcc otherwise sinks each
     // group of loads to its use, leaving one array's load in flight at a time)
 #pragma unroll
     for (int u = 0; u < ADAM_U; ++u) asm volatile("" : "+v"(pp[u]), "+v"(gg[u]), "+v"(mm[u]), "+v"(vv[u]));
+    if constexpr (EMA) {
+#pragma unroll
+      for (int u = 0; u < ADAM_U; ++u) asm volatile("" : "+v"(ee[u]));
+    }
 #pragma unroll
     for (int u = 0; u < ADAM_U; ++u) {
       const size_t i = base + (size_t)u * 256;
@@ -1067,9 +1111,12 @@ __global__ void __launch_bounds__(256) adam_kernel(adam_f4* __restrict__ p, cons
         float pc = pp[u][c], mc = mm[u][c], vc = vv[u][c];
         float gc = gg[u][c];
         if constexpr (SCALED) gc *= gs;
+        if constexpr (DECAY) pc *= keep;
         adam_one(pc, gc, mc, vc, b1c, b2, b2c, eps, neg_step, bc2s);
         pp[u][c] = pc, mm[u][c] = mc, vv[u][c] = vc;
+        if constexpr (EMA) ee[u][c] += (pc - ee[u][c]) * rate;
       }
+      if constexpr (EMA) __builtin_nontemporal_store(ee[u], e + i);
       __builtin_nontemporal_store(pp[u], p + i);
       __builtin_nontemporal_store(mm[u], m + i);
       __builtin_nontemporal_store(vv[u], v + i);
@@ -1095,7 +1142,7 @@ __global__ void __launch_bounds__(256) adam_kernel(adam_f4* __restrict__ p, cons
 }
 void adam_update(float* p, const float* g, float* m, float* v, size_t n, float b1, float b2, float eps,
                  const float* scal, bf16* shadow, size_t n_shadow, hipStream_t s, int grid_cap,
-                 const AdamTiles& tiles, const float* gscale) {
+                 const AdamTiles& tiles, const float* gscale, const AdamOpt& x) {
   require(tiles.n >= 0 && tiles.n <= AdamTiles::kMax, "adam: at most kMax tiled ranges");
   for (int t = 0; t < tiles.n; ++t)
     // (the tile formula needs only the element offset from the matrix start; 4-aligned so a thread's
@@ -1104,9 +1151,12 @@ void adam_update(float* p, const float* g, float* m, float* v, size_t n, float b
                 tiles.off[t] + tiles.len[t] <= (int64_t)n_shadow && tiles.dst[t],
             "adam: a tiled range must be whole 16-row blocks of 512-wide rows inside the shadow range");
   require(n % 4 == 0 && n_shadow % 4 == 0, "adam: arena size must be a multiple of 4");
+  require(!x.ema || x.ema_rate, "adam: an average needs its rate word");
   if (skip_mask() & 32) return;
   if (hz::active())
-    hz::op(s, "adam", {hz::rd(g, (int64_t)n * 4), hz::rd(scal, 8), hz::rd(gscale, 4), hz::wr(p, (int64_t)n * 4), hz::wr(m, (int64_t)n * 4),
+    hz::op(s, "adam", {hz::rd(g, (int64_t)n * 4), hz::rd(scal, 8), hz::rd(gscale, 4), hz::rd(x.decay, 4),
+                       hz::rd(x.ema ? x.ema_rate : nullptr, 4), hz::wr(x.ema, (int64_t)n * 4),
+                       hz::wr(p, (int64_t)n * 4), hz::wr(m, (int64_t)n * 4),
                        hz::wr(v, (int64_t)n * 4), hz::wr(shadow, (int64_t)n_shadow * 2),
                        hz::wr(tiles.n > 0 ? tiles.dst[0] : nullptr, tiles.n > 0 ? tiles.len[0] * 2 : 0),
                        hz::wr(tiles.n > 1 ? tiles.dst[1] : nullptr, tiles.n > 1 ? tiles.len[1] * 2 : 0),
@@ -1118,12 +1168,43 @@ void adam_update(float* p, const float* g, float* m, float* v, size_t n, float b
   constexpr int cap = 256;
   // grid_cap > 0: the caller's cap (an update on the step's critical path takes the whole chip)
   int grid = (int)std::min<size_t>((n4 + 256 * ADAM_U - 1) / (256 * ADAM_U), (size_t)(grid_cap > 0 ? grid_cap : cap));
-  if (gscale)
-    adam_kernel<const float*><<<grid, 256, 0, s>>>((adam_f4*)p, (const adam_f4*)g, (adam_f4*)m, (adam_f4*)v, n4, b1, b2,
-                                                   eps, scal, shadow, n_shadow, tiles, gscale);
-  else
-    adam_kernel<><<<grid, 256, 0, s>>>((adam_f4*)p, (const adam_f4*)g, (adam_f4*)m, (adam_f4*)v, n4, b1, b2, eps, scal,
-                                     shadow, n_shadow, tiles);
+  // the variant: one instantiation per set of options, the options in the pack's fixed order
+  auto launch = [&](auto... opt) {
+    adam_kernel<decltype(opt)...><<<grid, 256, 0, s>>>((adam_f4*)p, (const adam_f4*)g, (adam_f4*)m, (adam_f4*)v, n4, b1,
+                                                       b2, eps, scal, shadow, n_shadow, tiles, opt...);
+  };
+  auto with_ema = [&](auto... opt) {
+    if (x.ema) launch(opt..., AdamEmaArg{(adam_f4*)x.ema, x.ema_rate});
+    else launch(opt...);
+  };
+  auto with_decay = [&](auto... opt) {
+    if (x.decay) with_ema(opt..., AdamDecayArg{x.decay});
+    else with_ema(opt...);
+  };
+  if (gscale) with_decay(gscale);
+  else with_decay();
+  CAPGEN_HIP(hipGetLastError());
+}
+
+// ---- arena exchange (the averaged weights in and out of the parameter arena) ---------------------
+// a[i] <-> b[i] over n f32 (n % 4 == 0, 16-byte aligned): 16-B non-temporal accesses, grid-stride
+__global__ void __launch_bounds__(256) arena_swap_kernel(adam_f4* __restrict__ a, adam_f4* __restrict__ b, size_t n4) {
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n4; i += stride) {
+    const adam_f4 x = __builtin_nontemporal_load(a + i), y = __builtin_nontemporal_load(b + i);
+    __builtin_nontemporal_store(y, a + i);
+    __builtin_nontemporal_store(x, b + i);
+  }
+}
+void arena_swap(float* a, float* b, size_t n, hipStream_t s, int grid_cap) {
+  require(a != nullptr && b != nullptr, "arena_swap: null array");
+  require(n % 4 == 0, "arena_swap: the size must be a multiple of 4");
+  require(a + n <= b || b + n <= a, "arena_swap: the arrays overlap");
+  if (n == 0) return;
+  if (hz::active()) hz::op(s, "arena_swap", {hz::wr(a, (int64_t)n * 4), hz::wr(b, (int64_t)n * 4)});
+  const size_t n4 = n / 4;
+  const int grid = (int)std::min<size_t>((n4 + 255) / 256, (size_t)(grid_cap > 0 ? grid_cap : 2048));
+  arena_swap_kernel<<<grid, 256, 0, s>>>((adam_f4*)a, (adam_f4*)b, n4);
   CAPGEN_HIP(hipGetLastError());
 }
 

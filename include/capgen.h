@@ -145,6 +145,45 @@ int capgen_set_lr(capgen_t* h, float lr);
 int capgen_get_lr(capgen_t* h, float* lr);
 int capgen_set_grad_clip(capgen_t* h, float max_norm);
 int capgen_last_grad_norm(capgen_t* h, float* host_out);
+/* Decoupled weight decay (torch.optim.AdamW) and an exponential moving average of the parameters
+ * (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn(decay)), both inside the update kernel and
+ * both off by default: an engine that never calls these launches what it launched before and allocates
+ * nothing more.  Each combines with capgen_set_grad_clip and runs in every update (capgen_train_step,
+ * _indexed, _weighted, capgen_rl_finish, capgen_adam_step; under ZeRO-1 on this rank's chunks).
+ * Switching either between off and on drops the captured whole-step graph (not the forward graph); a
+ * new value while on lives in a device word and is read by the replay.
+ * capgen_set_weight_decay: p *= 1 - lr * wd before the Adam update of the same step, with the learning rate
+ * of that step; the factor is computed in double on the device and rounded once.  Decay covers every
+ * element of the arena (torch.optim.AdamW over all parameters); padding elements have zero parameter and
+ * zero gradient, so they stay zero.
+ * capgen_set_ema: after each update e += (p_new - e) * (1 - decay).  off -> on: the average becomes a copy
+ * of the current parameters and n_updates = 0 (AveragedModel's first update); the arena (one more f32
+ * arena) is allocated at the first enable.  on -> on: only the decay changes.  -> off: updating stops and
+ * the arena stays readable.  capgen_dp_init, which replaces the parameters by rank 0's,
+ * restarts an enabled average in the same way (a copy of them, n_updates = 0).  n_updates counts the updates issued while the average is on: a host counter,
+ * and graph replays count.  capgen_set_params while on and not swapped leaves the average alone.
+ * capgen_ema_info: the decay (0 = off), n_updates and whether the average is swapped in.
+ * capgen_get_ema (synchronous; fails only if the average was never enabled or on a size mismatch): the
+ * average's arena, laid out as the parameters.  It never refuses for staleness: after sharded (ZeRO-1)
+ * steps it holds this rank's chunks only until capgen_dp_sync_adam_state, which all-gathers the average
+ * too while it is on (as capgen_get_params under capgen_dp_debug_shard).
+ * capgen_set_ema_state: overwrite the arena and the counter of an enabled average (checkpoint restore).
+ * capgen_ema_swap: exchange the parameters and the average in place and rebuild the bf16 shadow and the
+ * weight tiles, so that forward, capgen_compute_loss, capgen_score_captions and every decoder run on the
+ * averaged weights and capgen_get_params returns them; a second call swaps back.  No pointer moves:
+ * cached graphs stay valid.  While swapped, every call that would update parameters fails before it
+ * launches anything, naming capgen_ema_swap: capgen_train_step, _indexed, _weighted (train != 0),
+ * capgen_rl_finish (train != 0), capgen_adam_step, capgen_set_params, capgen_set_adam_state,
+ * capgen_dp_init; capgen_set_ema may then change the decay only.  capgen_ema_swap fails while the average
+ * is off or was never enabled, and at world > 1 while this rank's average is stale (call
+ * capgen_dp_sync_adam_state on every rank first).
+ * Added without a change of CAPGEN_ABI_VERSION: no existing entry changed (backward compatible). */
+int capgen_set_weight_decay(capgen_t* h, float wd);  /* finite, >= 0; 0 = off (default) */
+int capgen_set_ema(capgen_t* h, float decay);        /* 0 = off (default), else in (0, 1) */
+int capgen_ema_info(capgen_t* h, float* decay, int64_t* n_updates, int* swapped);  /* any pointer may be null */
+int capgen_get_ema(capgen_t* h, float* host_dst, int64_t n);
+int capgen_set_ema_state(capgen_t* h, const float* host_src, int64_t n, int64_t n_updates);
+int capgen_ema_swap(capgen_t* h);
 /* TRANSFORMER.compute_loss (models.py:128-135): forward under no_grad. */
 int capgen_compute_loss(capgen_t* h, const void* feats, int feats_dtype, const float* pos, const int32_t* caps,
                         int B, int N, int T, float* loss_out, void* stream);
@@ -521,6 +560,18 @@ int capgen_debug_adam_scaled(float* p, const float* g, float* m, float* v, int64
                              float eps, int64_t* step, float* scal, void* shadow, int64_t n_shadow, int grid_cap,
                              int n_tiles, const int64_t* tile_off, const int64_t* tile_len, void* const* tile_dst,
                              const float* gscale, void* stream);
+/* capgen_debug_adam_scaled plus the optional parts of the update, each of which may be absent: gscale
+ * (null), weight_decay (0) -- p *= 1 - lr * weight_decay first -- and ema (null), n device floats updated
+ * as e += (p_new - e) * (1 - ema_decay).  scal holds 8 device floats here: the hook stores {lr,
+ * weight_decay, 1 - ema_decay} in scal[4..6] (synchronously) for the kernels to read, and the prepare
+ * kernel writes scal[2] only when weight_decay != 0.
+ * capgen_debug_arena_swap: a[i] <-> b[i] over n device floats (the kernel of capgen_ema_swap; grid_cap > 0
+ * caps the workgroups).  Fails (1), writing nothing, when n % 4 != 0, n < 0 or a pointer is null. */
+int capgen_debug_adam_ex(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
+                         float eps, int64_t* step, float* scal, void* shadow, int64_t n_shadow, int grid_cap,
+                         int n_tiles, const int64_t* tile_off, const int64_t* tile_len, void* const* tile_dst,
+                         const float* gscale, float weight_decay, float* ema, float ema_decay, void* stream);
+int capgen_debug_arena_swap(float* a, float* b, int64_t n, int grid_cap, void* stream);
 int capgen_debug_grad_norm(const float* g, int64_t n, float max_norm, int grid_cap, double* partials, int cap,
                            float* out2, void* stream);
 int capgen_debug_to_bf16(const float* src, void* dst, int64_t n, void* stream);
