@@ -2,7 +2,8 @@
 Transformer path of shao-chi/Image-Caption).  Host code here; kernels in libcapgen.so."""
 from .config import CapgenConfig, preset  # noqa: F401
 
-__all__ = ["CapgenConfig", "preset", "Engine", "Transformer", "PolicyNetwork", "TRANSFORMER", "SelfCriticNetwork"]
+__all__ = ["CapgenConfig", "preset", "Engine", "Transformer", "PolicyNetwork", "TRANSFORMER", "SelfCriticNetwork",
+           "Ensemble"]
 
 
 def __getattr__(name):
@@ -22,4 +23,7 @@ def __getattr__(name):
     if name == "SelfCriticNetwork":
         from .models import SelfCriticNetwork
         return SelfCriticNetwork
+    if name == "Ensemble":
+        from .ensemble import Ensemble
+        return Ensemble
     raise AttributeError(name)

@@ -79,6 +79,28 @@ def decode_constraints(no_repeat_ngram=0, min_length=0, end_id=-1, repetition_pe
     return c
 
 
+ENS_PROB, ENS_LOGPROB = 0, 1
+ENS_MODES = {"prob": ENS_PROB, "logprob": ENS_LOGPROB}
+
+
+class capgen_ensemble(C.Structure):
+    """capgen_ensemble (include/capgen.h): members[0] leads; weights is a host array, NULL = equal"""
+    _fields_ = [("members", C.POINTER(_P)), ("n_members", C.c_int32), ("weights", C.POINTER(C.c_float)),
+                ("mode", C.c_int32)]
+
+
+def ensemble(handles, weights=None, mode=ENS_PROB):
+    """The struct for capgen_ensemble_beam_nbest / capgen_ensemble_sample (it keeps its arrays alive)"""
+    hs = [h.value if isinstance(h, C.c_void_p) else h for h in handles]
+    e = capgen_ensemble()
+    e._members = (_P * len(hs))(*hs)
+    e.members, e.n_members, e.mode = C.cast(e._members, C.POINTER(_P)), len(hs), int(mode)
+    if weights is not None:
+        e._weights = (C.c_float * len(hs))(*[float(w) for w in weights])
+        e.weights = C.cast(e._weights, C.POINTER(C.c_float))
+    return e
+
+
 _SIGS = {
     "capgen_last_error": (C.c_char_p, []),
     "capgen_abi_version": (C.c_int, []),
@@ -125,6 +147,12 @@ _SIGS = {
     "capgen_set_decode_constraints": (C.c_int, [_P, C.POINTER(capgen_decode_constraints)]),
     "capgen_debug_constrain_logits": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int64, C.c_int,
                                                 C.POINTER(capgen_decode_constraints), _P]),
+    "capgen_ensemble_beam_nbest": (C.c_int, [C.POINTER(capgen_ensemble), _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P]),
+    "capgen_ensemble_sample": (C.c_int, [C.POINTER(capgen_ensemble), _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                         C.c_float, C.c_int, C.c_float, C.c_uint64, _P, _P, _P]),
+    "capgen_debug_ensemble_combine": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int,
+                                                _P, _P, _P]),
     "capgen_set_rng_seed": (C.c_int, [_P, C.c_uint64]),
     "capgen_debug_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int,
                                     _P, C.c_int64, C.c_int, C.c_int, _P, C.c_float, C.c_int, C.c_int, _P]),

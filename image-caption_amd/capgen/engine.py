@@ -54,6 +54,75 @@ def check_ema_decay(decay) -> float:
     return d
 
 
+def check_ensemble_args(engines, weights, mode):
+    """The argument rules of a capgen_ensemble that need no device (the library checks them again, and the
+    members' configs): returns (engines as a list, weights as floats or None, the mode's number).  Each
+    message names its argument."""
+    engines = list(engines)
+    if not 1 <= len(engines) <= 8:
+        raise ValueError(f"capgen ensemble: engines must hold 1 to 8 members, not {len(engines)}")
+    for k, e in enumerate(engines):
+        if any(e is o for o in engines[:k]):
+            raise ValueError(f"capgen ensemble: engines[{k}] is a duplicate member")
+    if mode not in _lib.ENS_MODES:
+        raise ValueError(f"capgen ensemble: mode must be 'prob' or 'logprob', not {mode!r}")
+    if weights is not None:
+        weights = [float(w) for w in weights]
+        if len(weights) != len(engines):
+            raise ValueError(f"capgen ensemble: weights must hold one value per member ({len(engines)}), "
+                             f"not {len(weights)}")
+        for k, w in enumerate(weights):
+            if not (0.0 < w < float("inf")):  # (false for a NaN)
+                raise ValueError(f"capgen ensemble: weights[{k}] must be finite and > 0, not {w}")
+    return engines, weights, _lib.ENS_MODES[mode]
+
+
+def ensemble_beam_nbest(engines, feats, pos, beam_size, end_id, length_penalty=0.0, n_best=1, weights=None,
+                        mode="prob"):
+    """Engine.beam_nbest over the averaged next-word distribution of several engines
+    (capgen_ensemble_beam_nbest): engines[0] leads -- its hypotheses, decode constraints, stream and device --
+    and every member decodes the same hypotheses with its own weights.  weights: one positive value per
+    member, normalised to sum 1 (None: equal); mode 'prob' averages the probabilities, 'logprob' the
+    log-probabilities.  Returns what Engine.beam_nbest returns, scored under the ensemble distribution."""
+    engines, weights, m = check_ensemble_args(engines, weights, mode)
+    lead = engines[0]
+    beam_size, n = check_beam_nbest_args(beam_size, end_id, length_penalty, n_best, lead.cfg.num_vocab)
+    f, ft, p, _ = lead._inputs(feats, pos)
+    B, N, _ = f.shape
+    T = lead.cfg.max_length
+    dev = lead.device
+    ids = torch.empty(n * B, T, dtype=torch.int64, device=dev)
+    score = torch.empty(n * B, dtype=torch.float32, device=dev)
+    logp = torch.empty(n * B, dtype=torch.float32, device=dev)
+    length = torch.empty(n * B, dtype=torch.int32, device=dev)
+    e = _lib.ensemble([x.h for x in engines], weights, m)
+    _lib.check(lead.lib.capgen_ensemble_beam_nbest(C.byref(e), _ptr(f), ft, _ptr(p), B, N, beam_size, int(end_id),
+                                                   float(length_penalty), n, _ptr(ids), _ptr(score), _ptr(logp),
+                                                   _ptr(length), _stream(dev)))
+    return ids.view(n, B, T), score.view(n, B), logp.view(n, B), length.view(n, B)
+
+
+def ensemble_sample(engines, feats, pos, n_samples=1, temperature=1.0, top_k=0, seed=0, want_logp=True, top_p=1.0,
+                    weights=None, mode="prob"):
+    """Engine.sample from the averaged next-word distribution of several engines (capgen_ensemble_sample;
+    members, weights and mode as ensemble_beam_nbest's).  Returns what Engine.sample returns; logp is each
+    token's log-probability under the ensemble distribution it was drawn from."""
+    engines, weights, m = check_ensemble_args(engines, weights, mode)
+    lead = engines[0]
+    f, ft, p, _ = lead._inputs(feats, pos)
+    B, N, _ = f.shape
+    n, T = int(n_samples), lead.cfg.max_length
+    rows = max(n, 0) * B
+    dev = lead.device
+    ids = torch.empty(rows, T + 1, dtype=torch.int64, device=dev)
+    logp = torch.empty(rows, T - 1, dtype=torch.float32, device=dev) if want_logp else None
+    e = _lib.ensemble([x.h for x in engines], weights, m)
+    _lib.check(lead.lib.capgen_ensemble_sample(C.byref(e), _ptr(f), ft, _ptr(p), B, N, n, float(temperature),
+                                               int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(ids),
+                                               _ptr(logp), _stream(dev)))
+    return ids.view(n, B, T + 1), (logp.view(n, B, T - 1) if want_logp else None)
+
+
 class Engine:
     def __init__(self, cfg: CapgenConfig, device="cuda:0"):
         self.cfg = cfg

@@ -10,6 +10,20 @@ void scst_rewards(const int64_t* target, int64_t target_ld, const int64_t* sampl
                   int start_id, int end_id, int null_id, int64_t dot_id, double cider_w, double bleu_w, double* out);
 }  // namespace capgen
 
+// an ensemble entry point: the checks, then body(leader, run) between ensemble_enter / ensemble_leave
+template <class F>
+static int ensemble_call(const capgen_ensemble* e, const char* who, void* stream, F&& body) {
+  return guarded([&] {
+    const EnsembleRun run = capgen_engine::checked_ensemble(e, who);
+    capgen_engine* h = run.m[0];
+    set_device(h);
+    hipStream_t cs = (hipStream_t)stream;
+    h->ensemble_enter(run, cs);
+    body(h, run);
+    h->ensemble_leave(run, cs);
+  });
+}
+
 extern "C" {
 
 const char* capgen_last_error(void) { return g_last_error.c_str(); }
@@ -334,6 +348,23 @@ int capgen_sample_nucleus(capgen_t* h, const void* feats, int ft, const float* p
                           void* stream) {
   return decode_call(h, stream, [&] {
     h->sample(feats, dt(ft), pos, B, N, n_samples, temperature, top_k, top_p, sd, ids_out, logp_out, h->es);
+  });
+}
+
+int capgen_ensemble_beam_nbest(const capgen_ensemble* e, const void* feats, int ft, const float* pos, int B, int N,
+                               int k, int end_id, float length_penalty, int n_best, int64_t* ids_out,
+                               float* score_out, float* logp_out, int32_t* len_out, void* stream) {
+  return ensemble_call(e, "ensemble_beam_nbest", stream, [&](capgen_engine* h, const EnsembleRun& run) {
+    h->beam_nbest(feats, dt(ft), pos, B, N, k, end_id, length_penalty, n_best, ids_out, score_out, logp_out, len_out,
+                  h->es, &run);
+  });
+}
+
+int capgen_ensemble_sample(const capgen_ensemble* e, const void* feats, int ft, const float* pos, int B, int N,
+                           int n_samples, float temperature, int top_k, float top_p, uint64_t sd, int64_t* ids_out,
+                           float* logp_out, void* stream) {
+  return ensemble_call(e, "ensemble_sample", stream, [&](capgen_engine* h, const EnsembleRun& run) {
+    h->sample(feats, dt(ft), pos, B, N, n_samples, temperature, top_k, top_p, sd, ids_out, logp_out, h->es, &run);
   });
 }
 

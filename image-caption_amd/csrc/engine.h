@@ -180,6 +180,14 @@ struct GenWS {
   int32_t *bfin, *bfin2, *blen, *blen2;  // beam_nbest: [R] finished flag and length of each hypothesis
 };
 
+// Ensemble decoding: a capgen_ensemble after its checks.  m[0] leads: the call runs on its stream, over its
+// hypotheses, selection state, decode constraints and outputs; the others only run their decoder steps.
+struct EnsembleRun {
+  std::vector<capgen_engine*> m;
+  float log_w[8];  // log of the weights, normalised in double to sum 1
+  int mode;        // CAPGEN_ENS_PROB / CAPGEN_ENS_LOGPROB
+};
+
 }  // namespace capgen
 
 using namespace capgen;
@@ -916,9 +924,18 @@ struct capgen_engine {
               hipStream_t s);
   void beam(const void* feats, DType ft, const float* pos, int B, int N, int k, int64_t* ids_out, hipStream_t s);
   void beam_nbest(const void* feats, DType ft, const float* pos, int B, int N, int k, int end_id, float alpha,
-                  int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, hipStream_t s);
-  void beam_run(const void* feats, DType ft, const float* pos, int B, int N, int k, const int* end_id, hipStream_t s);
+                  int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, hipStream_t s,
+                  const EnsembleRun* ens = nullptr);
+  void beam_run(const void* feats, DType ft, const float* pos, int B, int N, int k, const int* end_id, hipStream_t s,
+                const EnsembleRun* ens = nullptr);
   void sample(const void* feats, DType ft, const float* pos, int B, int N, int n, float temperature, int top_k,
-              float top_p, uint64_t sd, int64_t* ids_out, float* logp_out, hipStream_t s);
+              float top_p, uint64_t sd, int64_t* ids_out, float* logp_out, hipStream_t s,
+              const EnsembleRun* ens = nullptr);
+  static EnsembleRun checked_ensemble(const capgen_ensemble* e, const std::string& who);
+  void ensemble_begin(const EnsembleRun& ens, const void* feats, DType ft, const float* pos, int B, int N, int R,
+                      hipStream_t s);
+  void ensemble_step(const EnsembleRun& ens, int R, int Bimg, int N, int t, const int32_t* kv_row, hipStream_t s);
+  void ensemble_enter(const EnsembleRun& ens, hipStream_t cs);
+  void ensemble_leave(const EnsembleRun& ens, hipStream_t cs);
   void set_constraints(const capgen_decode_constraints* c);
 };

@@ -1,5 +1,5 @@
 // capgen engine -- decoding (model.py:101-200), KV-cached: the decode tiles and workspace, the
-// per-position decoder step, greedy, beam, beam_nbest and sample, and the decode constraints.
+// per-position decoder step, greedy, beam, beam_nbest and sample, the decode constraints, and ensemble decoding.
 #include "abi_util.h"
 #include "engine.h"
 
@@ -241,7 +241,8 @@ void capgen_engine::beam(const void* feats, DType ft, const float* pos, int B, i
 // END-aware selection kernels (always the log-softmax); finished rows still run through the decoder and
 // there is no early exit: nothing here waits for the device.  One more launch, beam_finish, at the end.
 void capgen_engine::beam_nbest(const void* feats, DType ft, const float* pos, int B, int N, int k, int end_id, float alpha,
-    int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, hipStream_t s) {
+    int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, hipStream_t s,
+    const EnsembleRun* ens) {
   require(k >= 1 && k <= 16 && k <= L.V, "beam_nbest: beam_size must be in [1, min(16, num_vocab)]");
   require(n_best >= 1 && n_best <= k, "beam_nbest: n_best must be in [1, beam_size]");
   require(end_id >= -1 && end_id < L.V, "beam_nbest: end_id must be in [-1, num_vocab)");
@@ -251,19 +252,23 @@ void capgen_engine::beam_nbest(const void* feats, DType ft, const float* pos, in
   require(ids_out != nullptr, "beam_nbest: null ids_out");
   require(dc.min_length == 0 || dc.end_id == end_id,
           "beam_nbest: end_id differs from the end_id of the decode constraints' min_length");
-  beam_run(feats, ft, pos, B, N, k, &end_id, s);
+  beam_run(feats, ft, pos, B, N, k, &end_id, s, ens);
   beam_finish(g.seq, g.bprob, g.blen, k, B, L.maxlen, alpha, n_best, ids_out, score_out, logp_out, len_out, s);
 }
 
 // The loop of beam (end_id == nullptr: the reference's search, model.py:135-200) and of beam_nbest: leaves
 // the k * B hypotheses in g.seq, their scores in g.bprob and, for beam_nbest, g.bfin / g.blen.
-void capgen_engine::beam_run(const void* feats, DType ft, const float* pos, int B, int N, int k, const int* end_id, hipStream_t s) {
+// ens (null: none): every step's logits are the ensemble's (ensemble_step below), nothing else changes.
+void capgen_engine::beam_run(const void* feats, DType ft, const float* pos, int B, int N, int k, const int* end_id, hipStream_t s,
+    const EnsembleRun* ens) {
   const int R = k * B, Tc = L.maxlen, Tw = L.maxlen;
-  begin_decode(feats, ft, pos, B, N, R, s);
+  if (ens) ensemble_begin(*ens, feats, ft, pos, B, N, R, s);
+  else begin_decode(feats, ft, pos, B, N, R, s);
   init_gen_ids(g.seq, R, Tw, g.ids, Tc, s);  // (Tw == Tc)
   // position 0: every beam holds <START>; top-k of beam 0's distribution (model.py:148-166)
   beam_kvrow(g.kvrow2, g.kvrow, Tc, -1, g.ids, B, R, s);  // [r][0] = r
   dec_step(R, B, N, 0, g.cache, g.ids, false, s);
+  if (ens) ensemble_step(*ens, R, B, N, 0, nullptr, s);
   // decode constraints edit the step's logits (and repair the slab stats) in front of beam_nbest's selection
   const bool constrained = end_id && dc.on();
   if (constrained) constrain_logits(g.logits, slab_decode() ? g.dstats : nullptr, R, L.V, g.ids, Tc, 0, dc, s);
@@ -310,6 +315,7 @@ void capgen_engine::beam_run(const void* feats, DType ft, const float* pos, int 
   select(0, nullptr, 1);  // (beam 0's finalists only: every source is beam 0 at t = 0)
   for (int t = 1; t < Tw - 1; ++t) {
     dec_step(R, B, N, t, g.cache, g.ids, false, s, g.kvrow);
+    if (ens) ensemble_step(*ens, R, B, N, t, g.kvrow, s);
     if (constrained) constrain_logits(g.logits, slab_decode() ? g.dstats : nullptr, R, L.V, g.ids, Tc, t, dc, s);
     select(t, g.bprob, k);
   }
@@ -323,7 +329,7 @@ void capgen_engine::beam_run(const void* feats, DType ft, const float* pos, int 
 // draws at site kSampleSite0 + t, above every dropout site (< 2048).  top_p < 1 cuts each position's
 // candidates to the nucleus (sample_nucleus, select.hip); top_p == 1 launches sample_softmax as before.
 void capgen_engine::sample(const void* feats, DType ft, const float* pos, int B, int N, int n, float temperature, int top_k,
-    float top_p, uint64_t sd, int64_t* ids_out, float* logp_out, hipStream_t s) {
+    float top_p, uint64_t sd, int64_t* ids_out, float* logp_out, hipStream_t s, const EnsembleRun* ens) {
   require(n >= 1 && n <= 16, "sample: n_samples must be in [1, 16]");
   require(temperature > 0.f && temperature < INFINITY, "sample: temperature must be > 0 and finite");
   require(top_k >= 0 && top_k <= 16 && top_k <= L.V, "sample: top_k must be in [0, min(16, num_vocab)]");
@@ -334,10 +340,12 @@ void capgen_engine::sample(const void* feats, DType ft, const float* pos, int B,
   const float inv_tau = 1.f / temperature;
   require(inv_tau > 0.f && inv_tau < INFINITY, "sample: temperature out of range");
   const int R = n * B, Tc = L.maxlen, W = L.maxlen + 1;
-  begin_decode(feats, ft, pos, B, N, R, s);
+  if (ens) ensemble_begin(*ens, feats, ft, pos, B, N, R, s);
+  else begin_decode(feats, ft, pos, B, N, R, s);
   init_gen_ids(ids_out, R, W, g.ids, Tc, s);
   for (int t = 0; t < L.maxlen - 1; ++t) {
     dec_step(R, B, N, t, g.cache, g.ids, false, s);
+    if (ens) ensemble_step(*ens, R, B, N, t, nullptr, s);
     if (dc.on()) constrain_logits(g.logits, slab_decode() ? g.dstats : nullptr, R, L.V, g.ids, Tc, t, dc, s);
     if (top_p == 1.f)
       sample_softmax(g.logits, R, L.V, inv_tau, top_k, sd, kSampleSite0 + (uint32_t)t, ids_out, W, t + 1,
@@ -346,6 +354,86 @@ void capgen_engine::sample(const void* feats, DType ft, const float* pos, int B,
       sample_nucleus(g.logits, R, L.V, inv_tau, top_k, top_p, sd, kSampleSite0 + (uint32_t)t, ids_out, W, t + 1,
                      g.ids + t + 1, Tc, logp_out, Tc - 1, t, nullptr, s);
   }
+}
+
+// ---- ensemble decoding (capgen_ensemble_beam_nbest / capgen_ensemble_sample; the fusing kernel and the
+// definition of the two modes: ensemble_combine, select.hip) ----
+// Members k < K decode the SAME hypotheses in lock-step: at every position each member runs its own decoder
+// step -- its own weights, encoder output, K/V cache and scratch -- on the leader's token table and beam K/V
+// row table, which dec_step takes as arguments, so nothing is copied; one launch then fuses the K logit rows
+// over the leader's (and rebuilds the leader's slab stats on the bf16 path), and the leader's constraints and
+// selection run on that as on its own logits.  Depth, width and dtype may differ between members; what the
+// shared tables and inputs fix may not.  Everything is enqueued on the leader's stream.
+
+// The checks of a capgen_ensemble, before anything is launched; each message names the member and the field
+EnsembleRun capgen_engine::checked_ensemble(const capgen_ensemble* e, const std::string& who) {
+  require(e != nullptr, who + ": null ensemble");
+  require(e->n_members >= 1 && e->n_members <= 8, who + ": n_members must be in [1, 8]");
+  require(e->members != nullptr, who + ": null members");
+  require(e->mode == CAPGEN_ENS_PROB || e->mode == CAPGEN_ENS_LOGPROB,
+          who + ": mode must be CAPGEN_ENS_PROB or CAPGEN_ENS_LOGPROB");
+  EnsembleRun r;
+  r.mode = e->mode;
+  const int K = e->n_members;
+  double sum = 0;
+  for (int k = 0; k < K; ++k) {
+    const std::string mk = who + ": member " + std::to_string(k);
+    capgen_engine* m = e->members[k];
+    require(m != nullptr, mk + ": null handle");
+    for (int j = 0; j < k; ++j) require(e->members[j] != m, mk + ": duplicate handle (same as member " + std::to_string(j) + ")");
+    const capgen_engine* m0 = e->members[0];
+    require(m->device == m0->device, mk + ": device differs from member 0's");
+    auto same = [&](int a, int b, const char* field) {
+      require(a == b, mk + ": " + field + " = " + std::to_string(a) + " differs from member 0's " + std::to_string(b));
+    };
+    same(m->cfg.num_vocab, m0->cfg.num_vocab, "num_vocab");
+    same(m->cfg.max_length, m0->cfg.max_length, "max_length");
+    same(m->cfg.pad_idx, m0->cfg.pad_idx, "pad_idx");
+    same(m->cfg.dim_features, m0->cfg.dim_features, "dim_features");
+    same(m->cfg.dim_positions, m0->cfg.dim_positions, "dim_positions");
+    const float w = e->weights ? e->weights[k] : 1.f;
+    require(std::isfinite(w) && w > 0.f, mk + ": weights[" + std::to_string(k) + "] must be finite and > 0");
+    sum += (double)w;
+    r.m.push_back(m);
+  }
+  for (int k = 0; k < K; ++k) {  // normalised in double, rounded to f32 once
+    const float w = (float)((double)(e->weights ? e->weights[k] : 1.f) / sum);
+    r.log_w[k] = logf(w);
+  }
+  return r;
+}
+
+// The call between the streams: the leader's enter / leave, and every other member's own stream ordered
+// against the call in both directions -- what the member had enqueued is done before the call touches its
+// buffers, and the host_sync(es) a member does before it re-plans a workspace covers this call.
+void capgen_engine::ensemble_enter(const EnsembleRun& ens, hipStream_t cs) {
+  enter(cs);
+  for (size_t k = 1; k < ens.m.size(); ++k) dep(ens.m[k]->es, es, ens.m[k]->ev_out);
+}
+void capgen_engine::ensemble_leave(const EnsembleRun& ens, hipStream_t cs) {
+  for (size_t k = 1; k < ens.m.size(); ++k) dep(es, ens.m[k]->es, ens.m[k]->ev_in);
+  leave(cs);
+}
+
+// begin_decode of every member on s: every allocation of every member before anything is enqueued
+void capgen_engine::ensemble_begin(const EnsembleRun& ens, const void* feats, DType ft, const float* pos, int B, int N,
+    int R, hipStream_t s) {
+  for (capgen_engine* m : ens.m) m->ensure_acts(B, N, 2), m->ensure_gen(R, N), m->ensure_dtiles();
+  for (capgen_engine* m : ens.m) m->begin_decode(feats, ft, pos, B, N, R, s);
+}
+
+// After the leader's dec_step of position t: the other members' steps on the leader's ids (and kv_row), then
+// the fused distribution over the leader's logits
+void capgen_engine::ensemble_step(const EnsembleRun& ens, int R, int Bimg, int N, int t, const int32_t* kv_row,
+    hipStream_t s) {
+  const float* z[8];
+  z[0] = g.logits;
+  for (size_t k = 1; k < ens.m.size(); ++k) {
+    capgen_engine* m = ens.m[k];
+    m->dec_step(R, Bimg, N, t, m->g.cache, g.ids, false, s, kv_row);
+    z[k] = m->g.logits;
+  }
+  ensemble_combine(z, ens.log_w, (int)ens.m.size(), ens.mode, R, L.V, g.logits, slab_decode() ? g.dstats : nullptr, s);
 }
 
 // capgen_set_decode_constraints: c checked against the model and installed (null: none), its banned

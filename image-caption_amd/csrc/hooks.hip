@@ -580,6 +580,23 @@ int capgen_debug_constrain_logits(float* logits, void* stats, int R, int V, cons
   });
 }
 
+int capgen_debug_ensemble_combine(const float* const* logits, const float* weights, int K, int mode, int R, int V,
+                                  float* out, void* stats, void* stream) {
+  return guarded([&] {
+    require(K >= 1 && K <= 8, "debug_ensemble_combine: K must be in [1, 8]");
+    require(logits != nullptr, "debug_ensemble_combine: null logits");
+    double sum = 0;
+    for (int k = 0; k < K; ++k) {
+      const float w = weights ? weights[k] : 1.f;
+      require(std::isfinite(w) && w > 0.f, "debug_ensemble_combine: weights[" + std::to_string(k) + "] must be finite and > 0");
+      sum += (double)w;
+    }
+    float log_w[8];
+    for (int k = 0; k < K; ++k) log_w[k] = logf((float)((double)(weights ? weights[k] : 1.f) / sum));
+    ensemble_combine(logits, log_w, K, mode, R, V, out, reinterpret_cast<float2*>(stats), (hipStream_t)stream);
+  });
+}
+
 int capgen_debug_rl_rows(const float* logits, int M, int V, int32_t* sample, float* lse, float* logp_s, float* ent,
                          void* stream) {
   return guarded([&] {

@@ -85,6 +85,13 @@ struct DecodeConstraints {
 void constrain_logits(float* logits, float2* stats, int R, int V, const int32_t* ids, int64_t ids_ld, int t,
                       const DecodeConstraints& c, hipStream_t s);
 
+// Ensemble decoding (definition: select.hip): the K members' logits [R][V] of one step (logits: a HOST array
+// of K device pointers, log_w: K host floats, log of the normalised weights) fused into out [R][V], which
+// everything downstream reads as the step's logits.  mode 0: log sum_k w_k softmax_k, mode 1:
+// sum_k w_k log_softmax_k.  out may be logits[0]; stats (nullable): out's slab stats [R][ceil(V / 16)].
+void ensemble_combine(const float* const* logits, const float* log_w, int K, int mode, int R, int V, float* out,
+                      float2* stats, hipStream_t s);
+
 // the generation loops' bookkeeping
 // out [rows][width] (int64) and ids [rows][tcap] (int32): column 0 = <START> (1), the rest 0
 void init_gen_ids(int64_t* out, int rows, int width, int32_t* ids, int tcap, hipStream_t s);

@@ -2,7 +2,7 @@
 //
 // Greedy argmax, the beam step's per-row top-k and per-image merge, temperature / top-k / nucleus
 // sampling by Gumbel-max, the bf16 path's selection from the classifier's slab stats, the decode constraints
-// that edit a step's logits in front of a selection, and the beam bookkeeping of the generation loops.  Every selection orders candidates by (value descending, index
+// that edit a step's logits in front of a selection, the kernel that fuses an ensemble's logits into one row distribution, and the beam bookkeeping of the generation loops.  Every selection orders candidates by (value descending, index
 // ascending).  The pieces the kernels are built from -- the row in registers, the sorted per-thread
 // lists and the wave rounds over them, the block winner and the block reductions -- are in select_dev.h.
 #include <algorithm>
@@ -970,6 +970,212 @@ void constrain_logits(float* logits, float2* stats, int R, int V, const int32_t*
                                wr(logits, (int64_t)R * V * 4), wr(stats, stats ? (int64_t)R * ((V + 15) / 16) * 8 : 0)});
   }
   constrain_logits_kernel<<<R, 64, 0, s>>>(logits, stats, V, ids, ids_ld, t, c);
+  CAPGEN_HIP(hipGetLastError());
+}
+
+// ---- ensemble decoding: K members' logits of a step fused into one row distribution ----------
+// One launch between the members' decode steps and the leader's constraints / selection.  Members k < K
+// (1 <= K <= 8) hold logits z_k [R][V] of the same R hypotheses; l_k = z_k - logsumexp(z_k) is member k's
+// log-softmax row and lw_k = log w_k the log of its (normalised, positive) weight.  Row r of out gets
+// - mode 0 (prob, the arithmetic mean of the probabilities): y[v] = log sum_k w_k exp(l_k[v]), evaluated as
+//   a = lw_k + l_k[v], m = max_k a, y = m + log(sum_k exp(a - m)): the largest term contributes exactly 1, so
+//   y is finite wherever one member's logit is, however far every exp(l_k[v]) itself underflows;
+// - mode 1 (logprob, the weighted geometric mean): y[v] = sum_k w_k l_k[v] with w_k = exp(lw_k), summed in
+//   member order.  Not normalised: the selection's own log-softmax does that.
+// y = -inf only where a member logit is -inf (mode 0: every member's), so -inf keeps its meaning of "blocked"
+// for everything downstream, which reads y as the step's logits.  out may be member 0's buffer: every
+// element is read (in both passes) by the thread that later stores it, and the second pass starts behind a
+// workgroup barrier.
+// stats (nullable): {max, sum __expf(y - max)} of every 16-column slab of the STORED y, the form of the
+// classifier epilogue (GemmArgs::dec_stats) and in its order -- four columns per lane in column order, then
+// the xor-1 and xor-2 exchanges -- with columns at or past V counting as -inf and an empty slab {-inf, 0}.
+// The kernel: one workgroup of 256 threads per row, nothing shared between rows, so a row's bits do not
+// depend on R or the grid.  Pass 1 reads each member row once, every thread keeping an online (max, sum
+// __expf) per member over its columns 4 (tid + 256 u) .. + 3, merged over the wave by xor exchanges (both
+// partners compute the same commutative merge) and over the four waves in wave order: lse_k.  Pass 2 reads
+// the rows again -- the same workgroup, back to back, so from L2 -- and stores y.  16-byte loads and stores
+// where V % 4 == 0 (a lane's four columns are a quarter slab, four neighbouring lanes a slab); otherwise a
+// scalar form of the same two passes, and the slab stats from the stored row in a third step, as
+// constrain_logits repairs them.
+struct EnsembleArgs {
+  const float* z[8];
+  float lw[8];
+};
+
+// (m, s) <- the online-softmax merge of (m, s) and (m2, s2); an empty side has m = -inf, s = 0
+__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
+  const float M = fmaxf(m, m2);
+  const float a = m > -INFINITY ? s * expf(m - M) : 0.f, b = m2 > -INFINITY ? s2 * expf(m2 - M) : 0.f;
+  m = M, s = a + b;
+}
+// the fused value of one column from the members' logits zk and log-normalisers
+template <int K>
+__device__ __forceinline__ float ensemble_one(const float (&zk)[K], const float (&lse)[K], const float (&lw)[K],
+                                              const float (&w)[K], int mode) {
+  if (mode == 1) {
+    float y = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) y += w[k] * (zk[k] - lse[k]);
+    return y;
+  }
+  float a[K], m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < K; ++k) a[k] = lw[k] + (zk[k] - lse[k]), m = fmaxf(m, a[k]);
+  if constexpr (K == 1) return m;
+  // the terms are <= 1 and their sum is in [1, K]: the fast exp and log are good to a few 1e-7 absolute here.
+  // Every member blocked: the sum is 0 and its log -inf (no branch, never NaN)
+  const float mm = m > -INFINITY ? m : 0.f;
+  float se = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) se += __expf(a[k] - mm);
+  return mm + __logf(se);
+}
+
+template <int K, bool VEC>
+__global__ void __launch_bounds__(256) ensemble_combine_kernel(EnsembleArgs A, int mode, int V, float* out,
+                                                               float2* stats) {
+  __shared__ float sm[K][4], ss[K][4];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t row = (int64_t)r * V;
+  constexpr int W = VEC ? 4 : 1;  // columns per thread and round
+  const int rounds = (V + 256 * W - 1) / (256 * W);  // (uniform: every lane takes part in the exchanges)
+  float m[K], s[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) m[k] = -INFINITY, s[k] = 0.f;
+  for (int u = 0; u < rounds; ++u) {
+    const int c = W * (tid + 256 * u);
+    if (c >= V) continue;
+    float x[K][W];
+#pragma unroll
+    for (int k = 0; k < K; ++k) load_f<float, W>(A.z[k] + row + c, x[k]);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float mx = x[k][0];
+#pragma unroll
+      for (int i = 1; i < W; ++i) mx = fmaxf(mx, x[k][i]);
+      // (branch-free: while everything so far is -inf the shift is 0, and exp(-inf) adds 0)
+      const float M = fmaxf(m[k], mx), Ms = M > -INFINITY ? M : 0.f;
+      float q = s[k] * __expf(m[k] - Ms);
+#pragma unroll
+      for (int i = 0; i < W; ++i) q += __expf(x[k][i] - Ms);
+      m[k] = M, s[k] = q;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    lse_merge(m[k], s[k], lane_xchg<1>(m[k]), lane_xchg<1>(s[k]));
+    lse_merge(m[k], s[k], lane_xchg<2>(m[k]), lane_xchg<2>(s[k]));
+    lse_merge(m[k], s[k], lane_xchg<4>(m[k]), lane_xchg<4>(s[k]));
+    lse_merge(m[k], s[k], lane_xchg<8>(m[k]), lane_xchg<8>(s[k]));
+    lse_merge(m[k], s[k], lane_xchg<16>(m[k]), lane_xchg<16>(s[k]));
+    lse_merge(m[k], s[k], lane_xchg<32>(m[k]), lane_xchg<32>(s[k]));
+    if (lane == 0) sm[k][wave] = m[k], ss[k][wave] = s[k];
+  }
+  __syncthreads();  // (also: every read of pass 1 is done before a store of pass 2 -- out may be z[0])
+  float lse[K], lw[K], w[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    float mk = sm[k][0], sk = ss[k][0];
+#pragma unroll
+    for (int v = 1; v < 4; ++v) lse_merge(mk, sk, sm[k][v], ss[k][v]);
+    lse[k] = mk + logf(sk);
+    lw[k] = A.lw[k], w[k] = expf(A.lw[k]);
+  }
+  float* y = out + row;
+  float2* st = stats ? stats + (int64_t)r * ((V + 15) / 16) : nullptr;
+  for (int u = 0; u < rounds; ++u) {
+    const int c = W * (tid + 256 * u);
+    const bool on = c < V;
+    float o[W];
+    if (on) {
+      float x[K][W];
+#pragma unroll
+      for (int k = 0; k < K; ++k) load_f<float, W>(A.z[k] + row + c, x[k]);
+#pragma unroll
+      for (int i = 0; i < W; ++i) {
+        float zk[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) zk[k] = x[k][i];
+        o[i] = ensemble_one<K>(zk, lse, lw, w, mode);
+      }
+      store_f<float, W>(y + c, o);
+    } else {
+#pragma unroll
+      for (int i = 0; i < W; ++i) o[i] = -INFINITY;
+    }
+    if constexpr (VEC) {
+      if (st) {  // (uniform) the slab of lanes 4 j .. 4 j + 3
+        float mx = fmaxf(fmaxf(o[0], o[1]), fmaxf(o[2], o[3]));
+        mx = fmaxf(mx, lane_xchg<1>(mx));
+        mx = fmaxf(mx, lane_xchg<2>(mx));
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) q += mx > -INFINITY ? __expf(o[i] - mx) : 0.f;  // (never NaN)
+        q += lane_xchg<1>(q);
+        q += lane_xchg<2>(q);
+        if (on && (lane & 3) == 0) st[c >> 4] = float2{mx, q};
+      }
+    }
+  }
+  if constexpr (!VEC) {
+    if (!st) return;  // (the whole workgroup)
+    workgroup_stores_visible();
+    for (int sl = tid; sl < (V + 15) / 16; sl += 256) {
+      const int c0 = sl * 16;
+      float v[16], mx = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        v[i] = c0 + i < V ? y[c0 + i] : -INFINITY;
+        mx = fmaxf(mx, v[i]);
+      }
+      float q[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        q[g] = 0.f;
+#pragma unroll
+        for (int i = 4 * g; i < 4 * g + 4; ++i) q[g] += mx > -INFINITY ? __expf(v[i] - mx) : 0.f;
+      }
+      st[sl] = float2{mx, (q[0] + q[1]) + (q[2] + q[3])};
+    }
+  }
+}
+
+void ensemble_combine(const float* const* logits, const float* log_w, int K, int mode, int R, int V, float* out,
+                      float2* stats, hipStream_t s) {
+  require(K >= 1 && K <= 8, "ensemble_combine: K must be in [1, 8]");
+  require(mode == 0 || mode == 1, "ensemble_combine: mode must be 0 (prob) or 1 (logprob)");
+  require(logits && log_w && out && R >= 1 && V >= 1, "ensemble_combine: need logits, weights, out and R, V >= 1");
+  EnsembleArgs A{};
+  bool vec = V % 4 == 0 && (uintptr_t)out % 16 == 0;
+  for (int k = 0; k < K; ++k) {
+    require(logits[k] != nullptr, "ensemble_combine: null logits of member " + std::to_string(k));
+    require(std::isfinite(log_w[k]), "ensemble_combine: log weight of member " + std::to_string(k) + " is not finite");
+    A.z[k] = logits[k], A.lw[k] = log_w[k];
+    vec = vec && (uintptr_t)logits[k] % 16 == 0;
+  }
+  if (hz::active()) {
+    using namespace hz;
+    Rgn rg[10];
+    for (int k = 0; k < K; ++k) rg[k] = rd(logits[k], (int64_t)R * V * 4);
+    rg[K] = wr(out, (int64_t)R * V * 4);
+    rg[K + 1] = wr(stats, stats ? (int64_t)R * ((V + 15) / 16) * 8 : 0);
+    op(s, "ensemble_combine", rg, (size_t)K + 2);
+  }
+  auto launch = [&](auto kc) {
+    constexpr int KC = decltype(kc)::value;
+    if (vec) ensemble_combine_kernel<KC, true><<<R, 256, 0, s>>>(A, mode, V, out, stats);
+    else ensemble_combine_kernel<KC, false><<<R, 256, 0, s>>>(A, mode, V, out, stats);
+  };
+  switch (K) {
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    case 3: launch(std::integral_constant<int, 3>{}); break;
+    case 4: launch(std::integral_constant<int, 4>{}); break;
+    case 5: launch(std::integral_constant<int, 5>{}); break;
+    case 6: launch(std::integral_constant<int, 6>{}); break;
+    case 7: launch(std::integral_constant<int, 7>{}); break;
+    default: launch(std::integral_constant<int, 8>{}); break;
+  }
   CAPGEN_HIP(hipGetLastError());
 }
 

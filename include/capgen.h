@@ -269,6 +269,37 @@ typedef struct capgen_decode_constraints {
 } capgen_decode_constraints;
 int capgen_set_decode_constraints(capgen_t* h, const capgen_decode_constraints* c);
 
+/* Ensemble decoding: one search, or one set of draws, over the averaged next-word distribution of several
+ * engines (seeds, cross-entropy and self-critical checkpoints, raw and averaged weights).  Member 0 leads:
+ * it owns the hypotheses, the selection state, the decode constraints (the other members' are ignored) and
+ * the outputs, and the call runs on its stream.  At every position each member runs its own decoder step --
+ * own weights, encoder output and K/V cache -- on the leader's token histories, giving l_k = log-softmax of
+ * member k's logits; one launch writes over the leader's logits
+ *   CAPGEN_ENS_PROB:    y[v] = log sum_k w_k exp(l_k[v])   (finite even where every exp underflows in f32)
+ *   CAPGEN_ENS_LOGPROB: y[v] = sum_k w_k l_k[v]            (the selection's own log-softmax normalises it)
+ * and the constraints and the selection of the single-engine call read y as that step's logits; returned
+ * scores and log-probabilities are the ensemble distribution's.  weights: HOST, n_members values, finite
+ * and > 0, normalised to sum 1 in double and rounded to f32 once; NULL: equal.  n_members in [1, 8]; the
+ * members are distinct engines on one device with equal num_vocab, max_length, pad_idx, dim_features and
+ * dim_positions (depth, width and dtype may differ); a call that breaks a rule fails before anything is
+ * launched, naming the member and the field.  With one member both modes are the single engine's call up
+ * to f32 rounding.  The remaining arguments, their ranges and the output layouts are those of
+ * capgen_beam_nbest / capgen_sample_nucleus after h.  Definition: csrc/select.hip (ensemble_combine).
+ * Added without a change of CAPGEN_ABI_VERSION: no existing entry changed (backward compatible). */
+enum { CAPGEN_ENS_PROB = 0, CAPGEN_ENS_LOGPROB = 1 };
+typedef struct capgen_ensemble {
+  capgen_t* const* members;  /* members[0] leads */
+  int32_t n_members;
+  const float* weights;      /* HOST, nullable */
+  int32_t mode;
+} capgen_ensemble;
+int capgen_ensemble_beam_nbest(const capgen_ensemble* e, const void* feats, int feats_dtype, const float* pos, int B,
+                               int N, int beam_size, int end_id, float length_penalty, int n_best, int64_t* ids_out,
+                               float* score_out, float* logp_out, int32_t* len_out, void* stream);
+int capgen_ensemble_sample(const capgen_ensemble* e, const void* feats, int feats_dtype, const float* pos, int B, int N,
+                           int n_samples, float temperature, int top_k, float top_p, uint64_t seed, int64_t* ids_out,
+                           float* logp_out, void* stream);
+
 /* Decode scoring of capgen_greedy / capgen_beam: 0 (default) = Transformer (argmax of Softmax,
  * beams accumulate probabilities, model.py:124-128,183); 1 = PolicyNetwork, the SCST model
  * (argmax of LogSoftmax, beams accumulate log-probabilities, model_RL.py:72,126-127,157,182). */
@@ -629,6 +660,12 @@ int capgen_debug_beam_finish(const int64_t* seq, const float* logp, const int32_
  * c as capgen_set_decode_constraints takes it (banned on the host), without the max_length ranges. */
 int capgen_debug_constrain_logits(float* logits, void* stats, int R, int V, const int32_t* ids, int64_t ids_ld,
                                   int t, const capgen_decode_constraints* c, void* stream);
+/* The ensemble's one launch per step (definition: csrc/select.hip): logits is a HOST array of K device
+ * pointers to f32 [R][V]; weights HOST, K values > 0 (NULL: equal), normalised as capgen_ensemble's; mode
+ * CAPGEN_ENS_PROB / CAPGEN_ENS_LOGPROB; out [R][V] f32 device, may be logits[0]; stats (nullable): out's slab
+ * stats [R][ceil(V / 16)] float2 {max, sum exp(v - max)}, as capgen_debug_gemm_classifier writes them. */
+int capgen_debug_ensemble_combine(const float* const* logits, const float* weights, int K, int mode, int R, int V,
+                                  float* out, void* stats, void* stream);
 /* SCST kernels (csrc/rl.hip): rows = sample (argmax log-softmax), lse, logp[sample], entropy per logit
  * row; image = per-image masked mean entropy, scal[0] = sum(mask); numer: scal[1] = -sum logp mask
  * score; loss: out = {(1-w) lm + w struct, lm, struct}; grad = the fully scaled d loss / d logits. */

@@ -11,6 +11,10 @@ against beam5 of the same run.
 beam5ec / sample1c: beam5e / sample1 under decode constraints (Engine.set_decode_constraints: no_repeat_ngram 2,
 min_length 5, repetition_penalty 1.2, three banned words) -- one more launch per decode step, read against
 beam5e / sample1 of the same run.
+ens2_beam5e / ens3_beam5e / ens2_sample1: beam5e / sample1 over an ensemble of 2 / 3 engines (random-init C2
+weights of seeds 0, 1, 2; capgen.engine.ensemble_beam_nbest / ensemble_sample, equal weights, mode 'prob'): every
+member's decoder steps plus one ensemble_combine launch per step, read against K x the single-engine mode of the
+same run.
 
 Algorithmic work (KV-cached count): beam-5 1776.7 GFLOP, greedy 699.4 GFLOP per
 256-image batch.  The reference CPU path (no KV cache) took 25.0 s (beam) / 5.87 s (greedy) per
@@ -26,13 +30,14 @@ sys.path.insert(0, os.path.join(REPO, "image-caption_amd"))
 import torch  # noqa: E402
 
 from capgen import _lib, preset  # noqa: E402
-from capgen.engine import Engine  # noqa: E402
+from capgen.engine import Engine, ensemble_beam_nbest, ensemble_sample  # noqa: E402
 from capgen.params import reference_init_state_dict  # noqa: E402
 from capgen.synthetic import synthetic_batch  # noqa: E402
 
 GFLOP = {"beam5": 1776.7, "greedy": 699.4, "sample1": 699.4, "sample5": 1776.7,  # (sampleN: its decode steps')
          "sample1p": 699.4, "sample5p": 1776.7, "beam5e": 1776.7, "beam5en": 1776.7,
-         "beam5ec": 1776.7, "sample1c": 699.4}
+         "beam5ec": 1776.7, "sample1c": 699.4,
+         "ens2_beam5e": 2 * 1776.7, "ens3_beam5e": 3 * 1776.7, "ens2_sample1": 2 * 699.4}  # (every member's steps)
 
 
 def main():
@@ -40,13 +45,25 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1, help="untimed calls first (the first one tunes GEMM shapes and sizes the workspaces)")
-    ap.add_argument("--modes", default="beam5,greedy", help="of beam5, greedy, sample1, sample5, sample1p, sample5p, beam5e, beam5en, beam5ec, sample1c")
+    ap.add_argument("--modes", default="beam5,greedy", help="of beam5, greedy, sample1, sample5, sample1p, sample5p, beam5e, beam5en, beam5ec, sample1c, "
+                    "ens2_beam5e, ens3_beam5e, ens2_sample1")
     args = ap.parse_args()
     cfg = preset("C2", dtype="bf16")
     dev = torch.device("cuda", 0)
     eng = Engine(cfg, dev)
     eng.load_state_dict({k: torch.from_numpy(v) for k, v in reference_init_state_dict(cfg, seed=0).items()})
     eng.set_training(False)
+    members = [eng]  # the ensemble modes' engines: created when the first of them runs
+
+    def ensemble(K):
+        while len(members) < K:
+            e = Engine(cfg, dev)
+            e.load_state_dict({k: torch.from_numpy(v)
+                               for k, v in reference_init_state_dict(cfg, seed=len(members)).items()})
+            e.set_training(False)
+            members.append(e)
+        return members[:K]
+
     B, N = args.batch, 36
     f, p, _ = synthetic_batch(B, N, cfg.encode_dim_features, cfg.encode_dim_positions, cfg.max_length,
                               cfg.num_vocab, seed=7)
@@ -59,7 +76,10 @@ def main():
             "beam5e": lambda: eng.beam_nbest(f, p, 5, 2, length_penalty=0.0, n_best=1),
             "beam5en": lambda: eng.beam_nbest(f, p, 5, 2, length_penalty=1.0, n_best=5),
             "beam5ec": lambda: eng.beam_nbest(f, p, 5, 2, length_penalty=0.0, n_best=1),
-            "sample1c": lambda: eng.sample(f, p, n_samples=1, seed=1)}
+            "sample1c": lambda: eng.sample(f, p, n_samples=1, seed=1),
+            "ens2_beam5e": lambda: ensemble_beam_nbest(ensemble(2), f, p, 5, 2, length_penalty=0.0, n_best=1),
+            "ens3_beam5e": lambda: ensemble_beam_nbest(ensemble(3), f, p, 5, 2, length_penalty=0.0, n_best=1),
+            "ens2_sample1": lambda: ensemble_sample(ensemble(2), f, p, n_samples=1, seed=1)}
     for name, fn in runs.items():
         if name not in args.modes.split(","):
             continue
