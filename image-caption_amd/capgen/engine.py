@@ -77,15 +77,9 @@ def check_ensemble_args(engines, weights, mode):
     return engines, weights, _lib.ENS_MODES[mode]
 
 
-def ensemble_beam_nbest(engines, feats, pos, beam_size, end_id, length_penalty=0.0, n_best=1, weights=None,
-                        mode="prob"):
-    """Engine.beam_nbest over the averaged next-word distribution of several engines
-    (capgen_ensemble_beam_nbest): engines[0] leads -- its hypotheses, decode constraints, stream and device --
-    and every member decodes the same hypotheses with its own weights.  weights: one positive value per
-    member, normalised to sum 1 (None: equal); mode 'prob' averages the probabilities, 'logprob' the
-    log-probabilities.  Returns what Engine.beam_nbest returns, scored under the ensemble distribution."""
-    engines, weights, m = check_ensemble_args(engines, weights, mode)
-    lead = engines[0]
+def _beam_nbest(lead, call, feats, pos, beam_size, end_id, length_penalty, n_best):
+    """Engine.beam_nbest and ensemble_beam_nbest: lead's inputs and outputs; call(*arguments after the handle)
+    issues the C call"""
     beam_size, n = check_beam_nbest_args(beam_size, end_id, length_penalty, n_best, lead.cfg.num_vocab)
     f, ft, p, _ = lead._inputs(feats, pos)
     B, N, _ = f.shape
@@ -95,11 +89,36 @@ def ensemble_beam_nbest(engines, feats, pos, beam_size, end_id, length_penalty=0
     score = torch.empty(n * B, dtype=torch.float32, device=dev)
     logp = torch.empty(n * B, dtype=torch.float32, device=dev)
     length = torch.empty(n * B, dtype=torch.int32, device=dev)
-    e = _lib.ensemble([x.h for x in engines], weights, m)
-    _lib.check(lead.lib.capgen_ensemble_beam_nbest(C.byref(e), _ptr(f), ft, _ptr(p), B, N, beam_size, int(end_id),
-                                                   float(length_penalty), n, _ptr(ids), _ptr(score), _ptr(logp),
-                                                   _ptr(length), _stream(dev)))
+    _lib.check(call(_ptr(f), ft, _ptr(p), B, N, beam_size, int(end_id), float(length_penalty), n, _ptr(ids),
+                    _ptr(score), _ptr(logp), _ptr(length), _stream(dev)))
     return ids.view(n, B, T), score.view(n, B), logp.view(n, B), length.view(n, B)
+
+
+def _sample(lead, call, feats, pos, n_samples, temperature, top_k, seed, want_logp, top_p):
+    """Engine.sample and ensemble_sample, as _beam_nbest"""
+    f, ft, p, _ = lead._inputs(feats, pos)
+    B, N, _ = f.shape
+    n, T = int(n_samples), lead.cfg.max_length
+    rows = max(n, 0) * B
+    dev = lead.device
+    ids = torch.empty(rows, T + 1, dtype=torch.int64, device=dev)
+    logp = torch.empty(rows, T - 1, dtype=torch.float32, device=dev) if want_logp else None
+    _lib.check(call(_ptr(f), ft, _ptr(p), B, N, n, float(temperature), int(top_k), float(top_p),
+                    int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(ids), _ptr(logp), _stream(dev)))
+    return ids.view(n, B, T + 1), (logp.view(n, B, T - 1) if want_logp else None)
+
+
+def ensemble_beam_nbest(engines, feats, pos, beam_size, end_id, length_penalty=0.0, n_best=1, weights=None,
+                        mode="prob"):
+    """Engine.beam_nbest over the averaged next-word distribution of several engines
+    (capgen_ensemble_beam_nbest): engines[0] leads -- its hypotheses, decode constraints, stream and device --
+    and every member decodes the same hypotheses with its own weights.  weights: one positive value per
+    member, normalised to sum 1 (None: equal); mode 'prob' averages the probabilities, 'logprob' the
+    log-probabilities.  Returns what Engine.beam_nbest returns, scored under the ensemble distribution."""
+    engines, weights, m = check_ensemble_args(engines, weights, mode)
+    lead, e = engines[0], _lib.ensemble([x.h for x in engines], weights, m)
+    return _beam_nbest(lead, lambda *a: lead.lib.capgen_ensemble_beam_nbest(C.byref(e), *a), feats, pos, beam_size,
+                       end_id, length_penalty, n_best)
 
 
 def ensemble_sample(engines, feats, pos, n_samples=1, temperature=1.0, top_k=0, seed=0, want_logp=True, top_p=1.0,
@@ -108,19 +127,9 @@ def ensemble_sample(engines, feats, pos, n_samples=1, temperature=1.0, top_k=0, 
     members, weights and mode as ensemble_beam_nbest's).  Returns what Engine.sample returns; logp is each
     token's log-probability under the ensemble distribution it was drawn from."""
     engines, weights, m = check_ensemble_args(engines, weights, mode)
-    lead = engines[0]
-    f, ft, p, _ = lead._inputs(feats, pos)
-    B, N, _ = f.shape
-    n, T = int(n_samples), lead.cfg.max_length
-    rows = max(n, 0) * B
-    dev = lead.device
-    ids = torch.empty(rows, T + 1, dtype=torch.int64, device=dev)
-    logp = torch.empty(rows, T - 1, dtype=torch.float32, device=dev) if want_logp else None
-    e = _lib.ensemble([x.h for x in engines], weights, m)
-    _lib.check(lead.lib.capgen_ensemble_sample(C.byref(e), _ptr(f), ft, _ptr(p), B, N, n, float(temperature),
-                                               int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(ids),
-                                               _ptr(logp), _stream(dev)))
-    return ids.view(n, B, T + 1), (logp.view(n, B, T - 1) if want_logp else None)
+    lead, e = engines[0], _lib.ensemble([x.h for x in engines], weights, m)
+    return _sample(lead, lambda *a: lead.lib.capgen_ensemble_sample(C.byref(e), *a), feats, pos, n_samples,
+                   temperature, top_k, seed, want_logp, top_p)
 
 
 class Engine:
@@ -526,18 +535,8 @@ class Engine:
         come back ordered by score = logp / max(len, 1) ** length_penalty (0.0: logp itself).  Always scored
         with the log-softmax.  Returns (ids int64 [n, B, T] laid out as beam's, zeros after <END>; score f32
         [n, B]; logp f32 [n, B]; len int32 [n, B]: tokens through <END>, T - 1 where it never came)."""
-        beam_size, n = check_beam_nbest_args(beam_size, end_id, length_penalty, n_best, self.cfg.num_vocab)
-        f, ft, p, _ = self._inputs(feats, pos)
-        B, N, _ = f.shape
-        T = self.cfg.max_length
-        ids = torch.empty(n * B, T, dtype=torch.int64, device=self.device)
-        score = torch.empty(n * B, dtype=torch.float32, device=self.device)
-        logp = torch.empty(n * B, dtype=torch.float32, device=self.device)
-        length = torch.empty(n * B, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.capgen_beam_nbest(self.h, _ptr(f), ft, _ptr(p), B, N, beam_size, int(end_id),
-                                              float(length_penalty), n, _ptr(ids), _ptr(score), _ptr(logp),
-                                              _ptr(length), _stream(self.device)))
-        return ids.view(n, B, T), score.view(n, B), logp.view(n, B), length.view(n, B)
+        return _beam_nbest(self, lambda *a: self.lib.capgen_beam_nbest(self.h, *a), feats, pos, beam_size, end_id,
+                           length_penalty, n_best)
 
     def set_decode_constraints(self, no_repeat_ngram=0, min_length=0, end_id=-1, repetition_penalty=1.0, banned=()):
         """What beam_nbest and sample may not say, from now on (capgen_set_decode_constraints; greedy and beam
@@ -561,16 +560,8 @@ class Engine:
         (ids int64 [n, B, T+1] laid out as greedy's, logp f32 [n, B, T-1] or None): logp holds each
         token's log-probability under the distribution it was drawn from.  One (seed, inputs,
         weights) gives one result."""
-        f, ft, p, _ = self._inputs(feats, pos)
-        B, N, _ = f.shape
-        n, T = int(n_samples), self.cfg.max_length
-        rows = max(n, 0) * B
-        ids = torch.empty(rows, T + 1, dtype=torch.int64, device=self.device)
-        logp = torch.empty(rows, T - 1, dtype=torch.float32, device=self.device) if want_logp else None
-        _lib.check(self.lib.capgen_sample_nucleus(self.h, _ptr(f), ft, _ptr(p), B, N, n, float(temperature),
-                                                  int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                  _ptr(ids), _ptr(logp), _stream(self.device)))
-        return ids.view(n, B, T + 1), (logp.view(n, B, T - 1) if want_logp else None)
+        return _sample(self, lambda *a: self.lib.capgen_sample_nucleus(self.h, *a), feats, pos, n_samples, temperature,
+                       top_k, seed, want_logp, top_p)
 
     # ---- SCST (SelfCriticNetwork) -------------------------------------------------------
     def rl_sample(self, feats, pos, caps):

@@ -169,7 +169,7 @@ struct GenWS {
   void *x, *x1, *x2, *q, *att, *tmp, *h, *E;
   float *mean, *rstd, *Pc, *logits;
   float2* dstats;         // bf16 decode: classifier slab stats [R][ceil(V/16)] (GemmArgs::dec_stats)
-  float* cand_v;          // beam: each row's k finalists (beam_step_topk)
+  float* cand_v;          // beam: each row's k finalists (beam_step's two-launch forms)
   int32_t* cand_i;
   void* cache;            // [Ld][R][Tcap][2d]: row r's K/V of position t at [l][r][t]
   int32_t *ids, *ids2;    // [R][Tcap]
@@ -451,7 +451,7 @@ struct capgen_engine {
   // MFMA attention kernel (0: the grouped VALU decode kernel, attention.hip)
   bool cross_mfma_on = knob(Knob::DecodeCrossMfma) != 0;
   // CAPGEN_FUSED_BEAM_STEP: bf16 beam selection and reorder of a step as one launch per image
-  // (beam_slab_step; 0 restores the top-k, merge and three reorder launches)
+  // (beam_step with a reorder; 0 restores the top-k, merge and three reorder launches)
   bool fused_beam_step_on = knob(Knob::FusedBeamStep) != 0;
   // CAPGEN_SLAB_DECODE: bf16 decode: the classifier epilogue writes slab stats and the greedy / beam
   // selection reads k * 16 logits per row instead of the whole row (0: full-row kernels)

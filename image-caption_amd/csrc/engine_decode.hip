@@ -272,33 +272,31 @@ void capgen_engine::beam_run(const void* feats, DType ft, const float* pos, int 
   // decode constraints edit the step's logits (and repair the slab stats) in front of beam_nbest's selection
   const bool constrained = end_id && dc.on();
   if (constrained) constrain_logits(g.logits, slab_decode() ? g.dstats : nullptr, R, L.V, g.ids, Tc, 0, dc, s);
-  // bf16: the selection and the reorder of a step as one launch per image (beam_slab_step:
-  // CAPGEN_FUSED_BEAM_STEP=0 restores the top-k, merge and three reorder launches)
+  // The step's form (select.h: BeamStep).  bf16: the selection and the reorder as one launch per image
+  // (CAPGEN_FUSED_BEAM_STEP=0 restores the top-k, merge and three reorder launches); off that form the
+  // END-aware step takes the full-row kernel, which reads the f32 logits of either dtype
   const bool fused_step = slab_decode() && fused_beam_step_on && k <= 16 && Tw == Tc;
   if (end_id) {  // every hypothesis starts live with no tokens
     memset_async(g.bfin, sizeof(int32_t) * R, s);
     memset_async(g.blen, sizeof(int32_t) * R, s);
   }
+  BeamStep b;  // what no step changes; the double-buffered arrays are set per step
+  b.logits = g.logits, b.B = B, b.V = L.V, b.k = k, b.logsm = decode_logsm;
+  b.stats = fused_step || (slab_decode() && !end_id) ? g.dstats : nullptr;
+  b.cand_v = g.cand_v, b.cand_i = g.cand_i, b.out_src = g.bsrc, b.out_tok = g.btok;
   // The selection of position t over the k_in live beams per image with scores prev, and the reorder
   // behind it.  The K/V cache is never copied: row r writes its position-t K/V at [l][r][t] and reads
   // position j of its history from row kvrow[r][j] (the beam it descended from there); a reorder
   // moves only the ids / sequences and this [R][Tc] table
   auto select = [&](int t, const float* prev, int k_in) {
     // the END-aware step's state: read from bfin / blen, written to bfin2 / blen2, then swapped
-    const BeamEnd ended = end_id ? BeamEnd{g.bfin, g.blen, g.bfin2, g.blen2, *end_id} : BeamEnd{};
-    if (fused_step && end_id)
-      beam_slab_step_ended(g.logits, g.dstats, prev, k_in, B, L.V, k, g.bprob2, g.bsrc, g.btok, g.seq, g.seq2, Tw,
-                           g.ids, g.ids2, g.kvrow, g.kvrow2, Tc, t, ended, s);
-    else if (fused_step)
-      beam_slab_step(g.logits, g.dstats, prev, k_in, B, L.V, k, decode_logsm, g.bprob2, g.bsrc, g.btok, g.seq,
-                     g.seq2, Tw, g.ids, g.ids2, g.kvrow, g.kvrow2, Tc, t, s);
-    else if (end_id)  // (off the fused path: the full-row kernel, which reads the f32 logits of either dtype)
-      beam_step_topk_ended(g.logits, prev, k_in, B, L.V, k, g.cand_v, g.cand_i, g.bprob2, g.bsrc, g.btok, ended, s);
-    else if (slab_decode())
-      beam_step_topk_slab(g.logits, g.dstats, prev, k_in, B, L.V, k, decode_logsm, g.cand_v, g.cand_i, g.bprob2,
-                          g.bsrc, g.btok, s);
-    else
-      beam_step_topk(g.logits, prev, k_in, B, L.V, k, decode_logsm, g.cand_v, g.cand_i, g.bprob2, g.bsrc, g.btok, s);
+    const BeamEnd ended{g.bfin, g.blen, g.bfin2, g.blen2, end_id ? *end_id : -1};
+    BeamReorder ro;
+    ro.seq_src = g.seq, ro.seq_dst = g.seq2, ro.ids_src = g.ids, ro.ids_dst = g.ids2;
+    ro.kv_src = g.kvrow, ro.kv_dst = g.kvrow2, ro.Tw = Tw, ro.Tc = Tc, ro.t = t;
+    b.prev = prev, b.k_in = k_in, b.out_prob = g.bprob2;
+    b.end = end_id ? &ended : nullptr, b.reorder = fused_step ? &ro : nullptr;
+    beam_step(b, s);
     std::swap(g.bprob, g.bprob2);
     if (end_id) std::swap(g.bfin, g.bfin2), std::swap(g.blen, g.blen2);
     if (!fused_step) {
@@ -347,12 +345,8 @@ void capgen_engine::sample(const void* feats, DType ft, const float* pos, int B,
     dec_step(R, B, N, t, g.cache, g.ids, false, s);
     if (ens) ensemble_step(*ens, R, B, N, t, nullptr, s);
     if (dc.on()) constrain_logits(g.logits, slab_decode() ? g.dstats : nullptr, R, L.V, g.ids, Tc, t, dc, s);
-    if (top_p == 1.f)
-      sample_softmax(g.logits, R, L.V, inv_tau, top_k, sd, kSampleSite0 + (uint32_t)t, ids_out, W, t + 1,
-                     g.ids + t + 1, Tc, logp_out, Tc - 1, t, s);
-    else
-      sample_nucleus(g.logits, R, L.V, inv_tau, top_k, top_p, sd, kSampleSite0 + (uint32_t)t, ids_out, W, t + 1,
-                     g.ids + t + 1, Tc, logp_out, Tc - 1, t, nullptr, s);
+    sample_nucleus(g.logits, R, L.V, inv_tau, top_k, top_p, sd, kSampleSite0 + (uint32_t)t, ids_out, W, t + 1,
+                   g.ids + t + 1, Tc, logp_out, Tc - 1, t, nullptr, s);
   }
 }
 

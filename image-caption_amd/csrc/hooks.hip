@@ -502,16 +502,23 @@ int capgen_debug_slab_argmax(const float* logits, const void* stats, int B, int 
   });
 }
 
+// the three beam-step hooks' descriptor: what every form takes
+static BeamStep debug_beam_step(const float* logits, const void* stats, const float* prev, int k_in, int B, int V,
+                                int k, int logsm, float* out_prob, int32_t* out_src, int32_t* out_tok) {
+  BeamStep b;
+  b.logits = logits, b.stats = reinterpret_cast<const float2*>(stats), b.prev = prev;
+  b.k_in = k_in, b.B = B, b.V = V, b.k = k, b.logsm = logsm;
+  b.out_prob = out_prob, b.out_src = out_src, b.out_tok = out_tok;
+  return b;
+}
+
 int capgen_debug_beam_step_topk(const float* logits, const void* stats, const float* prev, int k_in, int B, int V,
                                 int k, int logsm, float* cand_v, int32_t* cand_i, float* out_prob, int32_t* out_src,
                                 int32_t* out_tok, void* stream) {
   return guarded([&] {
-    const hipStream_t s = (hipStream_t)stream;
-    if (stats)
-      beam_step_topk_slab(logits, reinterpret_cast<const float2*>(stats), prev, k_in, B, V, k, logsm, cand_v, cand_i,
-                          out_prob, out_src, out_tok, s);
-    else
-      beam_step_topk(logits, prev, k_in, B, V, k, logsm, cand_v, cand_i, out_prob, out_src, out_tok, s);
+    BeamStep b = debug_beam_step(logits, stats, prev, k_in, B, V, k, logsm, out_prob, out_src, out_tok);
+    b.cand_v = cand_v, b.cand_i = cand_i;
+    beam_step(b, (hipStream_t)stream);
   });
 }
 
@@ -521,8 +528,12 @@ int capgen_debug_beam_slab_step(const float* logits, const void* stats, const fl
                                 int32_t* ids_dst, const int32_t* kv_src, int32_t* kv_dst, int Tc, int t, void* stream) {
   return guarded([&] {
     require(t >= 0, "debug_beam_slab_step: t >= 0");
-    beam_slab_step(logits, reinterpret_cast<const float2*>(stats), prev, k_in, B, V, k, logsm, out_prob, out_src,
-                   out_tok, seq_src, seq_dst, Tw, ids_src, ids_dst, kv_src, kv_dst, Tc, t, (hipStream_t)stream);
+    BeamReorder ro;
+    ro.seq_src = seq_src, ro.seq_dst = seq_dst, ro.Tw = Tw, ro.ids_src = ids_src, ro.ids_dst = ids_dst;
+    ro.kv_src = kv_src, ro.kv_dst = kv_dst, ro.Tc = Tc, ro.t = t;
+    BeamStep b = debug_beam_step(logits, stats, prev, k_in, B, V, k, logsm, out_prob, out_src, out_tok);
+    b.reorder = &ro;
+    beam_step(b, (hipStream_t)stream);
   });
 }
 
@@ -533,15 +544,17 @@ int capgen_debug_beam_step_ended(const float* logits, const void* stats, const f
                                  const int32_t* ids_src, int32_t* ids_dst, const int32_t* kv_src, int32_t* kv_dst,
                                  int Tc, int t, void* stream) {
   return guarded([&] {
-    const hipStream_t s = (hipStream_t)stream;
     const BeamEnd e{fin_src, len_src, fin_dst, len_dst, end_id};
-    if (stats) {
+    BeamReorder ro;
+    ro.seq_src = seq_src, ro.seq_dst = seq_dst, ro.Tw = Tw, ro.ids_src = ids_src, ro.ids_dst = ids_dst;
+    ro.kv_src = kv_src, ro.kv_dst = kv_dst, ro.Tc = Tc, ro.t = t;
+    BeamStep b = debug_beam_step(logits, stats, prev, k_in, B, V, k, 1, out_prob, out_src, out_tok);
+    b.cand_v = cand_v, b.cand_i = cand_i, b.end = &e;
+    if (stats) {  // the one-launch slab step (cand_v / cand_i unused); else the full-row kernels plus merge
       require(t >= 0, "debug_beam_step_ended: t >= 0");
-      beam_slab_step_ended(logits, reinterpret_cast<const float2*>(stats), prev, k_in, B, V, k, out_prob, out_src,
-                           out_tok, seq_src, seq_dst, Tw, ids_src, ids_dst, kv_src, kv_dst, Tc, t, e, s);
-    } else {
-      beam_step_topk_ended(logits, prev, k_in, B, V, k, cand_v, cand_i, out_prob, out_src, out_tok, e, s);
+      b.reorder = &ro;
     }
+    beam_step(b, (hipStream_t)stream);
   });
 }
 

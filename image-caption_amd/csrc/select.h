@@ -21,11 +21,6 @@ void sample_softmax(const float* logits, int R, int V, float inv_tau, int top_k,
 void sample_nucleus(const float* logits, int R, int V, float inv_tau, int top_k, float top_p, uint64_t seed,
                     uint32_t site, int64_t* ids_out, int64_t ids_ld, int col, int32_t* next_ids, int64_t next_ld,
                     float* logp_out, int64_t logp_ld, int logp_col, int32_t* count_out, hipStream_t s);
-// one beam-search step (model.py:183-190): rows j*B + i (j < k_in) of logits [k_in*B][V]; the
-// k best (prev[j*B+i] + softmax or log-softmax (logsm) of row j*B+i at v) per image i ->
-// out_prob/src/tok[sel*B + i]; cand_v/cand_i: k_in*B*k scratch (each row's k finalists)
-void beam_step_topk(const float* logits, const float* prev, int k_in, int B, int V, int k, int logsm, float* cand_v,
-                    int32_t* cand_i, float* out_prob, int32_t* out_src, int32_t* out_tok, hipStream_t s);
 // bf16 decode selection from the classifier epilogue's slab stats (GemmArgs::dec_stats: {max,
 // sum exp(v - max)} per row and 16-column slab, stats row stride S = ceil(V / 16)):
 // greedy -- argmax of the logits (first index on ties), read from the best slab only;
@@ -35,15 +30,6 @@ void beam_step_topk(const float* logits, const float* prev, int k_in, int B, int
 bool slab_select_ok(int V);
 void slab_argmax(const float* logits, const float2* stats, int B, int V, int64_t* ids_out, int64_t ids_ld, int col,
                  int32_t* next_ids, int64_t next_ld, hipStream_t s);
-// the bf16 beam step of every image in one launch (slab selection + merge + the reorder of the sequences,
-// ids and K/V row table into the *_dst buffers, chosen token at column t + 1)
-void beam_slab_step(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
-                    int logsm, float* out_prob, int32_t* out_src, int32_t* out_tok, const int64_t* seq_src,
-                    int64_t* seq_dst, int Tw, const int32_t* ids_src, int32_t* ids_dst, const int32_t* kv_src,
-                    int32_t* kv_dst, int Tc, int t, hipStream_t s);
-void beam_step_topk_slab(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
-                         int logsm, float* cand_v, int32_t* cand_i, float* out_prob, int32_t* out_src,
-                         int32_t* out_tok, hipStream_t s);
 
 // The END-aware beam step (beam_nbest; definition: select.hip): a finished source row offers one candidate
 // (its logp, token 0) whatever its logits hold, a live one its log-softmax scores (always, as logsm = 1
@@ -55,14 +41,39 @@ struct BeamEnd {
   int32_t* len_dst;
   int end_id;  // -1: nothing ever finishes
 };
-// full-row kernels + merge (as beam_step_topk) and the one-launch slab step (as beam_slab_step)
-void beam_step_topk_ended(const float* logits, const float* prev, int k_in, int B, int V, int k, float* cand_v,
-                          int32_t* cand_i, float* out_prob, int32_t* out_src, int32_t* out_tok, const BeamEnd& e,
-                          hipStream_t s);
-void beam_slab_step_ended(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
-                          float* out_prob, int32_t* out_src, int32_t* out_tok, const int64_t* seq_src,
-                          int64_t* seq_dst, int Tw, const int32_t* ids_src, int32_t* ids_dst, const int32_t* kv_src,
-                          int32_t* kv_dst, int Tc, int t, const BeamEnd& e, hipStream_t s);
+// the one-launch form's reorder behind its selection: sequences [.][Tw] (int64), ids and the K/V row table
+// [.][Tc] (int32) of the k * B new rows gathered from their source beams, chosen token at column t + 1 < Tw, Tc
+struct BeamReorder {
+  const int64_t* seq_src = nullptr;
+  int64_t* seq_dst = nullptr;
+  const int32_t *ids_src = nullptr, *kv_src = nullptr;
+  int32_t *ids_dst = nullptr, *kv_dst = nullptr;
+  int Tw = 0, Tc = 0, t = 0;  // (filled by name, as BeamStep: adjacent pointers of one type are easy to swap)
+};
+// One beam-search step (model.py:183-190): rows j * B + i (j < k_in) of logits [k_in * B][V]; per image i the
+// k best (prev[j * B + i] (null: 0) + softmax, or log-softmax with logsm, of row j * B + i at v) under (score
+// desc, j * V + v asc) -> out_prob / src / tok[sel * B + i].  k, k_in >= 1, k <= 16, k_in * k <= 256.
+// The three nullable members choose the kernels, and beam_step is the only place that knows how:
+//   end   stats  reorder   launches
+//   null  null   null      beam_row_topk_kernel (the exact full-row softmax) + beam_merge_kernel
+//   null  set    null      slab_row_topk_kernel + beam_merge_kernel
+//   null  set    set       beam_slab_step_kernel: selection, merge and reorder in one launch per image
+//   set   null   null      beam_row_topk_kernel<ENDED> + beam_merge_kernel<ENDED>
+//   set   set    set       beam_slab_step_kernel<ENDED>
+// Every other combination has no kernel and is refused.  stats: the rows' slab stats (above; V <= 16384); the
+// one-launch form also needs k_in <= 16.  cand_v / cand_i: k_in * B * k scratch (each row's k finalists) of
+// the two-launch forms only.  With end set the step always scores with the log-softmax: logsm is ignored.
+struct BeamStep {
+  const float* logits = nullptr;
+  const float2* stats = nullptr;
+  const float* prev = nullptr;
+  int k_in = 0, B = 0, V = 0, k = 0, logsm = 0;
+  float *cand_v = nullptr, *out_prob = nullptr;
+  int32_t *cand_i = nullptr, *out_src = nullptr, *out_tok = nullptr;
+  const BeamEnd* end = nullptr;          // null: the reference step
+  const BeamReorder* reorder = nullptr;  // null: selection only
+};
+void beam_step(const BeamStep& b, hipStream_t s);
 // the end of the search: score = logp (alpha == 0) or logp / max(len, 1)^alpha; per image the n_best of the
 // k hypotheses (rows j * B + i of seq [k * B][Tw], logp, len) under (score desc, beam asc) -> row
 // rank * B + i of ids_out [n_best * B][Tw], score_out, logp_out, len_out (the last three nullable)

@@ -199,29 +199,13 @@ __device__ __forceinline__ void beam_merge_wave(int n, int k, int lane, Load&& l
   }
 }
 
-// one wave per image over the rows' finalists in cand_v / cand_i [k_in * B][k]
+// one wave per image over the rows' finalists in cand_v / cand_i [k_in * B][k]; ENDED: the END-aware merge,
+// the same selection, then the new rows' fin / len from their sources'
+template <bool ENDED>
 __global__ void __launch_bounds__(64) beam_merge_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
                                                         int k_in, int B, int V, int k, float* __restrict__ out_prob,
-                                                        int32_t* __restrict__ out_src, int32_t* __restrict__ out_tok) {
-  const int i = blockIdx.x;
-  beam_merge_wave(
-      k_in * k, k, threadIdx.x,
-      [&](int e, float& v, int& c) {
-        const int64_t src = ((int64_t)(e / k) * B + i) * k + e % k;
-        v = cand_v[src], c = cand_i[src];
-      },
-      [&](int sel, float best, int bidx) {
-        out_prob[sel * B + i] = best;
-        out_src[sel * B + i] = bidx / V;
-        out_tok[sel * B + i] = bidx % V;
-      });
-}
-// the END-aware merge: the same selection, then the new rows' fin / len from their sources'
-__global__ void __launch_bounds__(64) beam_merge_ended_kernel(const float* __restrict__ cand_v,
-                                                              const int* __restrict__ cand_i, int k_in, int B, int V,
-                                                              int k, float* __restrict__ out_prob,
-                                                              int32_t* __restrict__ out_src,
-                                                              int32_t* __restrict__ out_tok, BeamEnd e) {
+                                                        int32_t* __restrict__ out_src, int32_t* __restrict__ out_tok,
+                                                        BeamEndArg<ENDED> e) {
   const int i = blockIdx.x;
   beam_merge_wave(
       k_in * k, k, threadIdx.x,
@@ -230,8 +214,14 @@ __global__ void __launch_bounds__(64) beam_merge_ended_kernel(const float* __res
         v = cand_v[src], c = cand_i[src];
       },
       [&](int sel, float best, int bidx) {
-        int src, tok;
-        beam_end_emit(e, sel, i, B, V, best, bidx, out_prob, out_src, out_tok, src, tok);
+        if constexpr (ENDED) {
+          int src, tok;
+          beam_end_emit(e, sel, i, B, V, best, bidx, out_prob, out_src, out_tok, src, tok);
+        } else {
+          out_prob[sel * B + i] = best;
+          out_src[sel * B + i] = bidx / V;
+          out_tok[sel * B + i] = bidx % V;
+        }
       });
 }
 
@@ -247,43 +237,11 @@ static void beam_row_topk(const float* logits, const float* prev, int rows, int 
   else beam_row_topk_kernel<KM, 0, 256, ENDED><<<rows, 256, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i, e);
 }
 
-void beam_step_topk(const float* logits, const float* prev, int k_in, int B, int V, int k, int logsm, float* cand_v,
-                    int32_t* cand_i, float* out_prob, int32_t* out_src, int32_t* out_tok, hipStream_t s) {
-  require(k >= 1 && k <= 16 && k_in >= 1 && k_in * k <= 256, "beam_step_topk: k in [1, 16]");
-  with_km(k, [&](auto km) {
-    beam_row_topk<decltype(km)::value>(logits, prev, k_in * B, B, V, k, logsm, cand_v, cand_i, s);
-  });
-  beam_merge_kernel<<<B, 64, 0, s>>>(cand_v, cand_i, k_in, B, V, k, out_prob, out_src, out_tok);
-  CAPGEN_HIP(hipGetLastError());
-}
-
 static void require_beam_end(const char* who, int V, const BeamEnd& e) {
   const std::string w(who);
   require(e.fin_src && e.len_src && e.fin_dst && e.len_dst, w + ": null fin / len");
   require(e.fin_src != e.fin_dst && e.len_src != e.len_dst, w + ": fin / len must be double-buffered");
   require(e.end_id >= -1 && e.end_id < V, w + ": end_id must be in [-1, num_vocab)");
-}
-
-void beam_step_topk_ended(const float* logits, const float* prev, int k_in, int B, int V, int k, float* cand_v,
-                          int32_t* cand_i, float* out_prob, int32_t* out_src, int32_t* out_tok, const BeamEnd& e,
-                          hipStream_t s) {
-  require(k >= 1 && k <= 16 && k_in >= 1 && k_in * k <= 256, "beam_step_topk_ended: k in [1, 16]");
-  require_beam_end("beam_step_topk_ended", V, e);
-  if (hz::active()) {
-    using namespace hz;
-    const int64_t Rin = (int64_t)k_in * B, R = (int64_t)k * B;
-    op(s, "beam_row_topk_ended", {rd(logits, Rin * V * 4), rd(prev, prev ? Rin * 4 : 0), rd(e.fin_src, Rin * 4),
-                                  wr(cand_v, Rin * k * 4), wr(cand_i, Rin * k * 4)});
-    op(s, "beam_merge_ended", {rd(cand_v, Rin * k * 4), rd(cand_i, Rin * k * 4), rd(e.fin_src, Rin * 4),
-                               rd(e.len_src, Rin * 4), wr(out_prob, R * 4), wr(out_src, R * 4), wr(out_tok, R * 4),
-                               wr(e.fin_dst, R * 4), wr(e.len_dst, R * 4)});
-  }
-  with_km(k, [&](auto km) {
-    beam_row_topk<decltype(km)::value, true>(logits, prev, k_in * B, B, V, k, 1, cand_v, cand_i, s, e);
-  });
-  beam_merge_ended_kernel<<<B, 64, 0, s>>>(cand_v, cand_i, k_in, B, V, k, out_prob, out_src, out_tok,
-                                           e);
-  CAPGEN_HIP(hipGetLastError());
 }
 
 // ---- sampled decoding: temperature / top-k / nucleus sampling by Gumbel-max, with the log-probability ----
@@ -731,54 +689,58 @@ __global__ void __launch_bounds__(1024) beam_slab_step_kernel(
   }
 }
 
-void beam_slab_step(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
-                    int logsm, float* out_prob, int32_t* out_src, int32_t* out_tok, const int64_t* seq_src,
-                    int64_t* seq_dst, int Tw, const int32_t* ids_src, int32_t* ids_dst, const int32_t* kv_src,
-                    int32_t* kv_dst, int Tc, int t, hipStream_t s) {
-  require(k >= 1 && k <= 16 && k_in >= 1 && k_in <= 16 && k_in * k <= 256, "beam_slab_step: k, k_in in [1, 16]");
-  require(slab_select_ok(V) && t + 1 < Tw && t + 1 < Tc, "beam_slab_step: V in [1, 16384], t + 1 < width");
-  if (hz::active()) {
-    using namespace hz;
-    const int R = k * B, S = (V + 15) / 16;
-    op(s, "beam_slab_step", {rd(logits, (int64_t)k_in * B * V * 4), rd(stats, (int64_t)k_in * B * S * 8),
-                             rd(prev, prev ? (int64_t)k_in * B * 4 : 0), wr(out_prob, (int64_t)k * B * 4),
-                             wr(out_src, (int64_t)k * B * 4), wr(out_tok, (int64_t)k * B * 4),
-                             rd(seq_src, (int64_t)R * Tw * 8), wr(seq_dst, (int64_t)R * Tw * 8),
-                             rd(ids_src, (int64_t)R * Tc * 4), wr(ids_dst, (int64_t)R * Tc * 4),
-                             rd(kv_src, (int64_t)R * Tc * 4), wr(kv_dst, (int64_t)R * Tc * 4)});
-  }
+// The launches of a checked BeamStep (the table in select.h); ea: the kernels' last argument
+template <bool ENDED>
+static void beam_step_launch(const BeamStep& b, BeamEndArg<ENDED> ea, hipStream_t s) {
+  const BeamReorder* ro = b.reorder;
+  const int k = b.k, k_in = b.k_in, B = b.B, V = b.V, rows = k_in * B, logsm = ENDED ? 1 : b.logsm;
   with_km(k, [&](auto km) {
-    beam_slab_step_kernel<decltype(km)::value><<<B, 64 * k_in, 0, s>>>(logits, stats, prev, k_in, B, V, k, logsm,
-                                                                       out_prob, out_src, out_tok, seq_src, seq_dst,
-                                                                       Tw, ids_src, ids_dst, kv_src, kv_dst, Tc, t,
-                                                                       NoBeamEnd{});
+    constexpr int KM = decltype(km)::value;
+    if (ro)
+      beam_slab_step_kernel<KM, ENDED><<<B, 64 * k_in, 0, s>>>(
+          b.logits, b.stats, b.prev, k_in, B, V, k, logsm, b.out_prob, b.out_src, b.out_tok, ro->seq_src, ro->seq_dst,
+          ro->Tw, ro->ids_src, ro->ids_dst, ro->kv_src, ro->kv_dst, ro->Tc, ro->t, ea);
+    else if (b.stats)
+      slab_row_topk_kernel<KM><<<(rows + 3) / 4, 256, 0, s>>>(b.logits, b.stats, b.prev, rows, B, V, k, logsm, b.cand_v,
+                                                              b.cand_i);
+    else beam_row_topk<KM, ENDED>(b.logits, b.prev, rows, B, V, k, logsm, b.cand_v, b.cand_i, s, ea);
   });
+  if (!ro) beam_merge_kernel<ENDED><<<B, 64, 0, s>>>(b.cand_v, b.cand_i, k_in, B, V, k, b.out_prob, b.out_src, b.out_tok, ea);
   CAPGEN_HIP(hipGetLastError());
 }
 
-void beam_slab_step_ended(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
-                          float* out_prob, int32_t* out_src, int32_t* out_tok, const int64_t* seq_src,
-                          int64_t* seq_dst, int Tw, const int32_t* ids_src, int32_t* ids_dst, const int32_t* kv_src,
-                          int32_t* kv_dst, int Tc, int t, const BeamEnd& e, hipStream_t s) {
-  require(k >= 1 && k <= 16 && k_in >= 1 && k_in <= 16 && k_in * k <= 256, "beam_slab_step_ended: k, k_in in [1, 16]");
-  require(slab_select_ok(V) && t + 1 < Tw && t + 1 < Tc, "beam_slab_step_ended: V in [1, 16384], t + 1 < width");
-  require_beam_end("beam_slab_step_ended", V, e);
-  if (hz::active()) {
+void beam_step(const BeamStep& b, hipStream_t s) {
+  const BeamEnd* e = b.end;
+  const BeamReorder* ro = b.reorder;
+  const int k = b.k, k_in = b.k_in, V = b.V;
+  require(k >= 1 && k <= 16 && k_in >= 1 && k_in * k <= 256, "beam_step: k in [1, 16], k_in * k in [1, 256]");
+  require(!ro || b.stats, "beam_step: reorder without stats (the one-launch form selects from the slab stats)");
+  require(!e || !b.stats || ro, "beam_step: end with stats but without reorder (no END-aware two-launch slab form)");
+  require(!b.stats || slab_select_ok(V), "beam_step: V must be in [1, 16384] with stats");
+  require(!ro || k_in <= 16, "beam_step: k_in in [1, 16] with reorder");
+  require(!ro || (ro->t + 1 < ro->Tw && ro->t + 1 < ro->Tc), "beam_step: t + 1 < width (Tw, Tc)");
+  if (e) require_beam_end("beam_step", V, *e);
+  if (hz::active() && (ro || e)) {  // (the two-launch reference forms record nothing)
     using namespace hz;
-    const int64_t R = (int64_t)k * B, Rin = (int64_t)k_in * B, S = (V + 15) / 16;
-    op(s, "beam_slab_step_ended", {rd(logits, Rin * V * 4), rd(stats, Rin * S * 8), rd(prev, prev ? Rin * 4 : 0),
-                                   rd(e.fin_src, Rin * 4), rd(e.len_src, Rin * 4), wr(e.fin_dst, R * 4),
-                                   wr(e.len_dst, R * 4), wr(out_prob, R * 4), wr(out_src, R * 4), wr(out_tok, R * 4),
-                                   rd(seq_src, R * Tw * 8), wr(seq_dst, R * Tw * 8), rd(ids_src, R * Tc * 4),
-                                   wr(ids_dst, R * Tc * 4), rd(kv_src, R * Tc * 4), wr(kv_dst, R * Tc * 4)});
+    const int64_t Rin = (int64_t)k_in * b.B, R = (int64_t)k * b.B, S = (V + 15) / 16;
+    const BeamEnd n = e ? *e : BeamEnd{};  // (null arrays: no region)
+    if (ro)
+      op(s, e ? "beam_slab_step_ended" : "beam_slab_step",
+         {rd(b.logits, Rin * V * 4), rd(b.stats, Rin * S * 8), rd(b.prev, b.prev ? Rin * 4 : 0), rd(n.fin_src, Rin * 4),
+          rd(n.len_src, Rin * 4), wr(n.fin_dst, R * 4), wr(n.len_dst, R * 4), wr(b.out_prob, R * 4),
+          wr(b.out_src, R * 4), wr(b.out_tok, R * 4), rd(ro->seq_src, R * ro->Tw * 8), wr(ro->seq_dst, R * ro->Tw * 8),
+          rd(ro->ids_src, R * ro->Tc * 4), wr(ro->ids_dst, R * ro->Tc * 4), rd(ro->kv_src, R * ro->Tc * 4),
+          wr(ro->kv_dst, R * ro->Tc * 4)});
+    else {
+      op(s, "beam_row_topk_ended", {rd(b.logits, Rin * V * 4), rd(b.prev, b.prev ? Rin * 4 : 0), rd(n.fin_src, Rin * 4),
+                                    wr(b.cand_v, Rin * k * 4), wr(b.cand_i, Rin * k * 4)});
+      op(s, "beam_merge_ended", {rd(b.cand_v, Rin * k * 4), rd(b.cand_i, Rin * k * 4), rd(n.fin_src, Rin * 4),
+                                 rd(n.len_src, Rin * 4), wr(b.out_prob, R * 4), wr(b.out_src, R * 4),
+                                 wr(b.out_tok, R * 4), wr(n.fin_dst, R * 4), wr(n.len_dst, R * 4)});
+    }
   }
-  with_km(k, [&](auto km) {
-    beam_slab_step_kernel<decltype(km)::value, true><<<B, 64 * k_in, 0, s>>>(logits, stats, prev, k_in, B, V, k, 1,
-                                                                             out_prob, out_src, out_tok, seq_src,
-                                                                             seq_dst, Tw, ids_src, ids_dst, kv_src,
-                                                                             kv_dst, Tc, t, e);
-  });
-  CAPGEN_HIP(hipGetLastError());
+  if (e) beam_step_launch<true>(b, *e, s);
+  else beam_step_launch<false>(b, NoBeamEnd{}, s);
 }
 
 // The end of the END-aware search (definition above), one wave per image, lane j = hypothesis j (k <= 16):
@@ -832,20 +794,6 @@ void beam_finish(const int64_t* seq, const float* logp, const int32_t* len, int 
     beam_finish_kernel<false><<<B, 64, 0, s>>>(seq, logp, len, k, B, Tw, alpha, n_best, ids_out, score_out, logp_out, len_out);
   else
     beam_finish_kernel<true><<<B, 64, 0, s>>>(seq, logp, len, k, B, Tw, alpha, n_best, ids_out, score_out, logp_out, len_out);
-  CAPGEN_HIP(hipGetLastError());
-}
-
-void beam_step_topk_slab(const float* logits, const float2* stats, const float* prev, int k_in, int B, int V, int k,
-                         int logsm, float* cand_v, int32_t* cand_i, float* out_prob, int32_t* out_src,
-                         int32_t* out_tok, hipStream_t s) {
-  require(k >= 1 && k <= 16 && k_in >= 1 && k_in * k <= 256, "beam_step_topk_slab: k in [1, 16]");
-  require(slab_select_ok(V), "beam_step_topk_slab: V must be in [1, 16384]");
-  const int rows = k_in * B;
-  with_km(k, [&](auto km) {
-    slab_row_topk_kernel<decltype(km)::value><<<(rows + 3) / 4, 256, 0, s>>>(logits, stats, prev, rows, B, V, k, logsm,
-                                                                             cand_v, cand_i);
-  });
-  beam_merge_kernel<<<B, 64, 0, s>>>(cand_v, cand_i, k_in, B, V, k, out_prob, out_src, out_tok);
   CAPGEN_HIP(hipGetLastError());
 }
 
