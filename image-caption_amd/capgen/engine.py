@@ -45,6 +45,35 @@ def check_beam_nbest_args(beam_size, end_id, length_penalty, n_best, num_vocab):
     return int(beam_size), int(n_best)
 
 
+def check_beam_diverse_args(beam_size, num_groups, diversity_penalty, end_id, length_penalty, n_best, num_vocab):
+    """The argument rules of capgen_beam_diverse, as check_beam_nbest_args; returns (beam_size, num_groups,
+    n_best) as ints.  n_best counts per group."""
+    if isinstance(num_groups, bool) or not isinstance(num_groups, (int, np.integer)):
+        raise TypeError(f"capgen beam_diverse: num_groups must be an int, not {type(num_groups).__name__}")
+    check_beam_nbest_args(beam_size, end_id, length_penalty, 1, num_vocab)  # (n_best: the per-group rule below)
+    if not 1 <= num_groups <= beam_size or beam_size % num_groups:
+        raise ValueError(f"capgen beam_diverse: num_groups must be in [1, beam_size] and divide it, not {num_groups}")
+    lam = float(diversity_penalty)
+    if not (0.0 <= lam < float("inf")):  # (false for a NaN)
+        raise ValueError(f"capgen beam_diverse: diversity_penalty must be finite and >= 0, not {diversity_penalty}")
+    if isinstance(n_best, bool) or not isinstance(n_best, (int, np.integer)):
+        raise TypeError(f"capgen beam_diverse: n_best must be an int, not {type(n_best).__name__}")
+    if not 1 <= n_best <= beam_size // num_groups:
+        raise ValueError(f"capgen beam_diverse: n_best must be in [1, beam_size / num_groups], not {n_best}")
+    return int(beam_size), int(num_groups), int(n_best)
+
+
+def check_diverse_call(beam_size, num_groups, diversity_penalty, end_id, length_penalty, n_best, num_vocab) -> bool:
+    """beam_captions' num_groups / diversity_penalty: False for the defaults (1, 0.0), which leave the call
+    the beam_nbest call it was; else the arguments are checked as beam_diverse's (a ValueError names the
+    offending one before the library is called) and True comes back."""
+    if not isinstance(num_groups, bool) and isinstance(num_groups, (int, np.integer)) and num_groups == 1 \
+            and float(diversity_penalty) == 0.0:
+        return False
+    check_beam_diverse_args(beam_size, num_groups, diversity_penalty, end_id, length_penalty, n_best, num_vocab)
+    return True
+
+
 def check_ema_decay(decay) -> float:
     """Engine.set_ema's argument rule, on the f32 the engine stores (0.99999999 rounds to 1.0f): the value
     to pass on, 0.0 for off; a ValueError naming the argument otherwise."""
@@ -94,6 +123,23 @@ def _beam_nbest(lead, call, feats, pos, beam_size, end_id, length_penalty, n_bes
     return ids.view(n, B, T), score.view(n, B), logp.view(n, B), length.view(n, B)
 
 
+def _beam_diverse(lead, call, feats, pos, beam_size, num_groups, diversity_penalty, end_id, length_penalty, n_best):
+    """Engine.beam_diverse and ensemble_beam_diverse, as _beam_nbest; n = num_groups * n_best rows per image"""
+    beam_size, G, nb = check_beam_diverse_args(beam_size, num_groups, diversity_penalty, end_id, length_penalty,
+                                               n_best, lead.cfg.num_vocab)
+    f, ft, p, _ = lead._inputs(feats, pos)
+    B, N, _ = f.shape
+    T, n = lead.cfg.max_length, G * nb
+    dev = lead.device
+    ids = torch.empty(n * B, T, dtype=torch.int64, device=dev)
+    score = torch.empty(n * B, dtype=torch.float32, device=dev)
+    logp = torch.empty(n * B, dtype=torch.float32, device=dev)
+    length = torch.empty(n * B, dtype=torch.int32, device=dev)
+    _lib.check(call(_ptr(f), ft, _ptr(p), B, N, beam_size, G, float(diversity_penalty), int(end_id),
+                    float(length_penalty), nb, _ptr(ids), _ptr(score), _ptr(logp), _ptr(length), _stream(dev)))
+    return ids.view(n, B, T), score.view(n, B), logp.view(n, B), length.view(n, B)
+
+
 def _sample(lead, call, feats, pos, n_samples, temperature, top_k, seed, want_logp, top_p):
     """Engine.sample and ensemble_sample, as _beam_nbest"""
     f, ft, p, _ = lead._inputs(feats, pos)
@@ -119,6 +165,16 @@ def ensemble_beam_nbest(engines, feats, pos, beam_size, end_id, length_penalty=0
     lead, e = engines[0], _lib.ensemble([x.h for x in engines], weights, m)
     return _beam_nbest(lead, lambda *a: lead.lib.capgen_ensemble_beam_nbest(C.byref(e), *a), feats, pos, beam_size,
                        end_id, length_penalty, n_best)
+
+
+def ensemble_beam_diverse(engines, feats, pos, beam_size, num_groups, diversity_penalty, end_id, length_penalty=0.0,
+                          n_best=1, weights=None, mode="prob"):
+    """Engine.beam_diverse over the averaged next-word distribution of several engines
+    (capgen_ensemble_beam_diverse; members, weights and mode as ensemble_beam_nbest's)."""
+    engines, weights, m = check_ensemble_args(engines, weights, mode)
+    lead, e = engines[0], _lib.ensemble([x.h for x in engines], weights, m)
+    return _beam_diverse(lead, lambda *a: lead.lib.capgen_ensemble_beam_diverse(C.byref(e), *a), feats, pos,
+                         beam_size, num_groups, diversity_penalty, end_id, length_penalty, n_best)
 
 
 def ensemble_sample(engines, feats, pos, n_samples=1, temperature=1.0, top_k=0, seed=0, want_logp=True, top_p=1.0,
@@ -537,6 +593,16 @@ class Engine:
         [n, B]; logp f32 [n, B]; len int32 [n, B]: tokens through <END>, T - 1 where it never came)."""
         return _beam_nbest(self, lambda *a: self.lib.capgen_beam_nbest(self.h, *a), feats, pos, beam_size, end_id,
                            length_penalty, n_best)
+
+    def beam_diverse(self, feats, pos, beam_size, num_groups, diversity_penalty, end_id, length_penalty=0.0, n_best=1):
+        """Diverse beam search (capgen_beam_diverse): beam_nbest with the beams split into num_groups groups,
+        each penalised by diversity_penalty per hypothesis of an earlier group that chose the same word at the
+        same position.  n_best <= beam_size / num_groups counts per group.  Returns (ids [G * n_best, B,
+        max_length] int64, score, logp f32 and len int32 [G * n_best, B]), group-major: row g * n_best + r is
+        group g's r-th best; logp is the model's log-probability, without the penalty.  num_groups = 1 is
+        beam_nbest."""
+        return _beam_diverse(self, lambda *a: self.lib.capgen_beam_diverse(self.h, *a), feats, pos, beam_size,
+                             num_groups, diversity_penalty, end_id, length_penalty, n_best)
 
     def set_decode_constraints(self, no_repeat_ngram=0, min_length=0, end_id=-1, repetition_penalty=1.0, banned=()):
         """What beam_nbest and sample may not say, from now on (capgen_set_decode_constraints; greedy and beam

@@ -9,7 +9,7 @@ import math
 
 import torch
 
-from .engine import check_ensemble_args, ensemble_beam_nbest, ensemble_sample
+from .engine import check_diverse_call, check_ensemble_args, ensemble_beam_diverse, ensemble_beam_nbest, ensemble_sample
 from .utils import sequence_logprob
 
 
@@ -37,15 +37,24 @@ class Ensemble:
         return [m.model.engine for m in self.models]
 
     def beam_captions(self, object_features, position_features, beam_size, length_penalty=0.0, n_best=1,
-                      no_repeat_ngram=0, min_length=0, repetition_penalty=1.0, banned_words=()):
-        """MODEL.beam_captions over the ensemble distribution: (captions, score), the same shapes; the
-        constraints are the leader's, for this call only."""
+                      no_repeat_ngram=0, min_length=0, repetition_penalty=1.0, banned_words=(), num_groups=1,
+                      diversity_penalty=0.0):
+        """MODEL.beam_captions over the ensemble distribution: (captions, score), the same shapes (num_groups
+        and diversity_penalty included); the constraints are the leader's, for this call only."""
         lead = self.leader
         end = -1 if lead.end_idx is None else int(lead.end_idx)
+        diverse = check_diverse_call(beam_size, num_groups, diversity_penalty, end, length_penalty, n_best,
+                                     lead.config.num_vocab)
         with lead._constrained(no_repeat_ngram, min_length, repetition_penalty, banned_words):
-            ids, score, _, _ = ensemble_beam_nbest(self._engines(), object_features, position_features, beam_size,
-                                                   end, length_penalty=length_penalty, n_best=n_best,
-                                                   weights=self.weights, mode=self.mode)
+            if diverse:
+                ids, score, _, _ = ensemble_beam_diverse(self._engines(), object_features, position_features,
+                                                         beam_size, num_groups, diversity_penalty, end,
+                                                         length_penalty=length_penalty, n_best=n_best,
+                                                         weights=self.weights, mode=self.mode)
+            else:
+                ids, score, _, _ = ensemble_beam_nbest(self._engines(), object_features, position_features,
+                                                       beam_size, end, length_penalty=length_penalty, n_best=n_best,
+                                                       weights=self.weights, mode=self.mode)
         host = ids.cpu().numpy()
         return [lead.decode_captions(host[j]) for j in range(host.shape[0])], score
 

@@ -126,6 +126,14 @@ class Transformer:
         return self.engine.beam_nbest(object_features, position_features, beam_size, end_id,
                                       length_penalty=length_penalty, n_best=n_best)
 
+    def beam_search_diverse(self, object_features, position_features, beam_size, num_groups, diversity_penalty,
+                            end_id, length_penalty=0.0, n_best=1):
+        """Diverse beam search (Vijayakumar et al. 2016): beam_search_nbest with the beams in num_groups groups,
+        later groups penalised for repeating earlier groups' words at a position.  Returns what
+        beam_search_nbest returns with num_groups * n_best rows, group-major -- Engine.beam_diverse."""
+        return self.engine.beam_diverse(object_features, position_features, beam_size, num_groups,
+                                        diversity_penalty, end_id, length_penalty=length_penalty, n_best=n_best)
+
     def sample_caption_vector(self, object_features, position_features, n_samples=1, temperature=1.0, top_k=0,
                               seed=None, top_p=1.0):
         """n_samples captions per image drawn from the model's distribution (temperature / top-k /

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .config import CapgenConfig
+from .engine import check_diverse_call
 from .model import PolicyNetwork, Transformer
 from .schedule import ScheduledSteps
 from .staging import HostBatchStager
@@ -80,7 +81,8 @@ class MODEL_init:
                 engine.set_decode_constraints()
 
     def beam_captions(self, object_features, position_features, beam_size, length_penalty=0.0, n_best=1,
-                      no_repeat_ngram=0, min_length=0, repetition_penalty=1.0, banned_words=()):
+                      no_repeat_ngram=0, min_length=0, repetition_penalty=1.0, banned_words=(), num_groups=1,
+                      diversity_penalty=0.0):
         """The n_best captions per image of a beam search that stops at <END> (generate_caption keeps the
         reference's search, which does not): (captions, score) -- n_best lists of B strings, best first, and
         their scores [n_best, B] (f32, on the model's device): the caption's log-probability through <END>
@@ -88,12 +90,25 @@ class MODEL_init:
         <END> searches to max_length.  Constraints, for this call only (Engine.set_decode_constraints): no
         n-gram of no_repeat_ngram words twice, no <END> before min_length tokens, the logits of the words
         already said scaled down by repetition_penalty, and banned_words (e.g. "<NULL>", "<START>", "<UNK>")
-        never; the scores are log-probabilities under the constrained distribution."""
+        never; the scores are log-probabilities under the constrained distribution.
+        num_groups > 1: diverse beam search -- the beams in num_groups groups, a later group penalised by
+        diversity_penalty for each earlier hypothesis that chose the same word at the same position; n_best
+        then counts per group (<= beam_size / num_groups) and num_groups * n_best lists come back, group-major
+        (all of group 0's first), with scores [num_groups * n_best, B] that never contain the penalty."""
         end = -1 if self.end_idx is None else int(self.end_idx)
+        diverse = check_diverse_call(beam_size, num_groups, diversity_penalty, end, length_penalty, n_best,
+                                     self.config.num_vocab)
         with self._constrained(no_repeat_ngram, min_length, repetition_penalty, banned_words):
-            ids, score, _, _ = self.model.beam_search_nbest(object_features=object_features,
-                                                            position_features=position_features, beam_size=beam_size,
-                                                            end_id=end, length_penalty=length_penalty, n_best=n_best)
+            if diverse:
+                ids, score, _, _ = self.model.beam_search_diverse(
+                    object_features=object_features, position_features=position_features, beam_size=beam_size,
+                    num_groups=num_groups, diversity_penalty=diversity_penalty, end_id=end,
+                    length_penalty=length_penalty, n_best=n_best)
+            else:
+                ids, score, _, _ = self.model.beam_search_nbest(object_features=object_features,
+                                                                position_features=position_features,
+                                                                beam_size=beam_size, end_id=end,
+                                                                length_penalty=length_penalty, n_best=n_best)
         host = ids.cpu().numpy()
         return [self.decode_captions(host[j]) for j in range(host.shape[0])], score
 

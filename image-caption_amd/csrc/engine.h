@@ -926,8 +926,11 @@ struct capgen_engine {
   void beam_nbest(const void* feats, DType ft, const float* pos, int B, int N, int k, int end_id, float alpha,
                   int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, hipStream_t s,
                   const EnsembleRun* ens = nullptr);
+  void beam_diverse(const void* feats, DType ft, const float* pos, int B, int N, int k, int G, float lambda, int end_id,
+                    float alpha, int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out,
+                    hipStream_t s, const EnsembleRun* ens = nullptr);
   void beam_run(const void* feats, DType ft, const float* pos, int B, int N, int k, const int* end_id, hipStream_t s,
-                const EnsembleRun* ens = nullptr);
+                const EnsembleRun* ens = nullptr, const BeamGroups* groups = nullptr);
   void sample(const void* feats, DType ft, const float* pos, int B, int N, int n, float temperature, int top_k,
               float top_p, uint64_t sd, int64_t* ids_out, float* logp_out, hipStream_t s,
               const EnsembleRun* ens = nullptr);

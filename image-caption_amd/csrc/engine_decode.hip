@@ -256,11 +256,42 @@ void capgen_engine::beam_nbest(const void* feats, DType ft, const float* pos, in
   beam_finish(g.seq, g.bprob, g.blen, k, B, L.maxlen, alpha, n_best, ids_out, score_out, logp_out, len_out, s);
 }
 
+// Diverse beam search (definition: select.hip): beam_nbest's search with the k beams split into num_groups
+// groups that are penalised, lambda per earlier hypothesis, for choosing the words earlier groups chose at the
+// same position.  beam_run's loop with the full-row END-aware top-k, the group merge and the three reorder
+// launches per token in either dtype (no fused slab form), then one beam_finish per group: n_best <= k / G of
+// each, output rows (g * n_best + rank) * B + b.  One group is beam_nbest itself, fused slab step included.
+void capgen_engine::beam_diverse(const void* feats, DType ft, const float* pos, int B, int N, int k, int G, float lambda,
+    int end_id, float alpha, int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out,
+    hipStream_t s, const EnsembleRun* ens) {
+  require(k >= 1 && k <= 16 && k <= L.V, "beam_diverse: beam_size must be in [1, min(16, num_vocab)]");
+  require(G >= 1 && G <= k && k % G == 0, "beam_diverse: num_groups must be in [1, beam_size] and divide it");
+  require(lambda >= 0.f && lambda < INFINITY, "beam_diverse: diversity_penalty must be finite and >= 0");  // (false for a NaN)
+  const int kg = k / G;
+  require(n_best >= 1 && n_best <= kg, "beam_diverse: n_best must be in [1, beam_size / num_groups]");
+  require(end_id >= -1 && end_id < L.V, "beam_diverse: end_id must be in [-1, num_vocab)");
+  require(alpha >= 0.f && alpha < INFINITY, "beam_diverse: length_penalty must be finite and >= 0");
+  require(N >= 1 && N <= 64, "beam_diverse: N must be in [1, 64]");
+  require(B >= 1, "beam_diverse: need B >= 1");
+  require(ids_out != nullptr, "beam_diverse: null ids_out");
+  require(dc.min_length == 0 || dc.end_id == end_id,
+          "beam_diverse: end_id differs from the end_id of the decode constraints' min_length");
+  if (G == 1) return beam_nbest(feats, ft, pos, B, N, k, end_id, alpha, n_best, ids_out, score_out, logp_out, len_out, s, ens);
+  const BeamGroups groups{G, lambda};
+  beam_run(feats, ft, pos, B, N, k, &end_id, s, ens, &groups);
+  const int64_t Tw = L.maxlen, in = (int64_t)kg * B, out = (int64_t)n_best * B;  // rows per group
+  for (int64_t h = 0; h < G; ++h)  // group h's hypotheses: rows h * k' * B .. of the k * B
+    beam_finish(g.seq + h * in * Tw, g.bprob + h * in, g.blen + h * in, kg, B, (int)Tw, alpha, n_best,
+                ids_out + h * out * Tw, score_out ? score_out + h * out : nullptr,
+                logp_out ? logp_out + h * out : nullptr, len_out ? len_out + h * out : nullptr, s);
+}
+
 // The loop of beam (end_id == nullptr: the reference's search, model.py:135-200) and of beam_nbest: leaves
 // the k * B hypotheses in g.seq, their scores in g.bprob and, for beam_nbest, g.bfin / g.blen.
 // ens (null: none): every step's logits are the ensemble's (ensemble_step below), nothing else changes.
+// groups (null: none; needs end_id): beam_diverse's selection, the hypotheses left group by group.
 void capgen_engine::beam_run(const void* feats, DType ft, const float* pos, int B, int N, int k, const int* end_id, hipStream_t s,
-    const EnsembleRun* ens) {
+    const EnsembleRun* ens, const BeamGroups* groups) {
   const int R = k * B, Tc = L.maxlen, Tw = L.maxlen;
   if (ens) ensemble_begin(*ens, feats, ft, pos, B, N, R, s);
   else begin_decode(feats, ft, pos, B, N, R, s);
@@ -275,7 +306,8 @@ void capgen_engine::beam_run(const void* feats, DType ft, const float* pos, int 
   // The step's form (select.h: BeamStep).  bf16: the selection and the reorder as one launch per image
   // (CAPGEN_FUSED_BEAM_STEP=0 restores the top-k, merge and three reorder launches); off that form the
   // END-aware step takes the full-row kernel, which reads the f32 logits of either dtype
-  const bool fused_step = slab_decode() && fused_beam_step_on && k <= 16 && Tw == Tc;
+  // (groups: the full-row top-k and the group merge; no fused form)
+  const bool fused_step = slab_decode() && fused_beam_step_on && k <= 16 && Tw == Tc && !groups;
   if (end_id) {  // every hypothesis starts live with no tokens
     memset_async(g.bfin, sizeof(int32_t) * R, s);
     memset_async(g.blen, sizeof(int32_t) * R, s);
@@ -283,7 +315,7 @@ void capgen_engine::beam_run(const void* feats, DType ft, const float* pos, int 
   BeamStep b;  // what no step changes; the double-buffered arrays are set per step
   b.logits = g.logits, b.B = B, b.V = L.V, b.k = k, b.logsm = decode_logsm;
   b.stats = fused_step || (slab_decode() && !end_id) ? g.dstats : nullptr;
-  b.cand_v = g.cand_v, b.cand_i = g.cand_i, b.out_src = g.bsrc, b.out_tok = g.btok;
+  b.cand_v = g.cand_v, b.cand_i = g.cand_i, b.out_src = g.bsrc, b.out_tok = g.btok, b.groups = groups;
   // The selection of position t over the k_in live beams per image with scores prev, and the reorder
   // behind it.  The K/V cache is never copied: row r writes its position-t K/V at [l][r][t] and reads
   // position j of its history from row kvrow[r][j] (the beam it descended from there); a reorder

@@ -558,6 +558,19 @@ int capgen_debug_beam_step_ended(const float* logits, const void* stats, const f
   });
 }
 
+int capgen_debug_beam_group_step(const float* logits, const float* prev, int k_in, int B, int V, int k, int num_groups,
+                                 float diversity_penalty, int end_id, const int32_t* fin_src, const int32_t* len_src,
+                                 int32_t* fin_dst, int32_t* len_dst, float* cand_v, int32_t* cand_i, float* out_prob,
+                                 int32_t* out_src, int32_t* out_tok, void* stream) {
+  return guarded([&] {
+    const BeamEnd e{fin_src, len_src, fin_dst, len_dst, end_id};
+    const BeamGroups gr{num_groups, diversity_penalty};
+    BeamStep b = debug_beam_step(logits, nullptr, prev, k_in, B, V, k, 1, out_prob, out_src, out_tok);
+    b.cand_v = cand_v, b.cand_i = cand_i, b.end = &e, b.groups = &gr;
+    beam_step(b, (hipStream_t)stream);
+  });
+}
+
 int capgen_debug_beam_finish(const int64_t* seq, const float* logp, const int32_t* len, int k, int B, int Tw,
                              float length_penalty, int n_best, int64_t* ids_out, float* score_out, float* logp_out,
                              int32_t* len_out, void* stream) {

@@ -50,17 +50,26 @@ struct BeamReorder {
   int32_t *ids_dst = nullptr, *kv_dst = nullptr;
   int Tw = 0, Tc = 0, t = 0;  // (filled by name, as BeamStep: adjacent pointers of one type are easy to swap)
 };
+// Diverse beam search (beam_diverse; definition: select.hip): the k beams are G groups of k / G, served in
+// order; a group's live candidates lose lambda for every hypothesis an earlier group of the image chose at
+// this step with the same token.  G divides k, lambda finite and >= 0.
+struct BeamGroups {
+  int G;
+  float lambda;
+};
 // One beam-search step (model.py:183-190): rows j * B + i (j < k_in) of logits [k_in * B][V]; per image i the
 // k best (prev[j * B + i] (null: 0) + softmax, or log-softmax with logsm, of row j * B + i at v) under (score
 // desc, j * V + v asc) -> out_prob / src / tok[sel * B + i].  k, k_in >= 1, k <= 16, k_in * k <= 256.
-// The three nullable members choose the kernels, and beam_step is the only place that knows how:
-//   end   stats  reorder   launches
-//   null  null   null      beam_row_topk_kernel (the exact full-row softmax) + beam_merge_kernel
-//   null  set    null      slab_row_topk_kernel + beam_merge_kernel
-//   null  set    set       beam_slab_step_kernel: selection, merge and reorder in one launch per image
-//   set   null   null      beam_row_topk_kernel<ENDED> + beam_merge_kernel<ENDED>
-//   set   set    set       beam_slab_step_kernel<ENDED>
-// Every other combination has no kernel and is refused.  stats: the rows' slab stats (above; V <= 16384); the
+// The four nullable members choose the kernels, and beam_step is the only place that knows how:
+//   end   stats  reorder  groups   launches
+//   null  null   null     null     beam_row_topk_kernel (the exact full-row softmax) + beam_merge_kernel
+//   null  set    null     null     slab_row_topk_kernel + beam_merge_kernel
+//   null  set    set      null     beam_slab_step_kernel: selection, merge and reorder in one launch per image
+//   set   null   null     null     beam_row_topk_kernel<ENDED> + beam_merge_kernel<ENDED>
+//   set   set    set      null     beam_slab_step_kernel<ENDED>
+//   set   null   null     set      beam_row_topk_kernel<ENDED> + beam_group_merge_kernel (k_in = 1 or k)
+// Every other combination has no kernel and is refused.  groups with G = 1 is no groups at all: the step is
+// the null-groups row of the same end / stats / reorder, whatever lambda.  stats: the rows' slab stats (above; V <= 16384); the
 // one-launch form also needs k_in <= 16.  cand_v / cand_i: k_in * B * k scratch (each row's k finalists) of
 // the two-launch forms only.  With end set the step always scores with the log-softmax: logsm is ignored.
 struct BeamStep {
@@ -72,6 +81,7 @@ struct BeamStep {
   int32_t *cand_i = nullptr, *out_src = nullptr, *out_tok = nullptr;
   const BeamEnd* end = nullptr;          // null: the reference step
   const BeamReorder* reorder = nullptr;  // null: selection only
+  const BeamGroups* groups = nullptr;    // null: one group
 };
 void beam_step(const BeamStep& b, hipStream_t s);
 // the end of the search: score = logp (alpha == 0) or logp / max(len, 1)^alpha; per image the n_best of the

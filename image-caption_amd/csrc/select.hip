@@ -98,6 +98,35 @@ void argmax_softmax(const float* logits, int B, int V, int64_t* ids_out, int64_t
 //   the form that does not divide), else s = logp / powf((float)max(len, 1), alpha).  Per image the
 //   hypotheses are ordered by (s descending, beam index ascending; a NaN s ranks as -inf) and the first
 //   n_best are written: tokens, s, logp and len.  A hypothesis that never finished has len = T - 1.
+//
+// ---- diverse beam search (beam_diverse; Vijayakumar et al. 2016: beam groups, Hamming diversity) ----
+// k = beam_size, G = num_groups (G divides k), k' = k / G; group g is beams g k' .. (g + 1) k' - 1; lambda =
+// diversity_penalty, finite and >= 0.  A hypothesis is exactly beam_nbest's, and logp stays the f32 running sum
+// of the model's token log-probabilities: the penalty orders candidates and is never added into logp.
+// At a position, for image i, the groups are served in order g = 0 .. G - 1:
+// - Count.  c_g(v) = the number of hypotheses selected at this position for groups h < g of image i that came
+//   from a live source and appended token v.  <END> counts like any word; the token 0 appended to a finished
+//   source does not count.
+// - Candidates of group g: those of beam_nbest's step, restricted to the group's own k' source rows (at step 0
+//   the only source is beam 0, for every group).  A live source j offers (logp_j + logsoftmax(row)[v] -
+//   lambda * c_g(v), flat index j * V + v); a finished one exactly (logp_j, j * V + 0), unpenalised, its logits
+//   never read.  The penalised score is the f32 candidate score minus the f32 product lambda * c (c = 0: the
+//   score itself).
+// - Selection.  The k' best under (penalised score descending, flat index ascending) become beams g k' + rank.
+// - Update: beam_nbest's, src being the absolute source beam.  The new logp is the unpenalised
+//   logp_j + logsoftmax[v] -- the very f32 the row kernel wrote as that finalist, not "penalised + lambda * c".
+// - Finish: beam_finish per group, the n_best <= k' best of each by logp / max(len, 1)^alpha, output row
+//   (g * n_best + rank) * B + i.  Decode constraints edit the logits before the selection and pruning uses
+//   the raw logp, both as for beam_nbest.
+// Consequences: G = 1 is beam_nbest bit for bit whatever lambda (it takes beam_nbest's launches); lambda = 0
+// with G > 1 gives G groups that each run beam_nbest(k') on their own -- identical groups; a penalised token has
+// c <= k - k'.
+// The kernels.  Penalties lower at most |S| <= g k' distinct tokens (S: the tokens chosen so far), so a row's
+// k' best penalised candidates lie among its k' + |S| <= k best unpenalised ones: a candidate outside them has
+// k' + |S| candidates ordered before it, at most |S| of which a penalty can move behind it.  Hence
+// beam_row_topk_kernel<ENDED> runs once over all k_in * B rows with k finalists per row, and
+// beam_group_merge_kernel, one wave per image, walks the groups in order over the group's rows' finalists.
+// The bound is tight: k = G = 16 with 16 equal rows takes each row's ranks 0 .. 15.
 
 // lane 0 of a merge, slot sel of image i: the selected (score, flat index) -> outputs and the new state
 __device__ __forceinline__ void beam_end_emit(const BeamEnd& e, int sel, int i, int B, int V, float best, int bidx,
@@ -223,6 +252,62 @@ __global__ void __launch_bounds__(64) beam_merge_kernel(const float* __restrict_
           out_tok[sel * B + i] = bidx % V;
         }
       });
+}
+
+// The group-sequential merge of diverse beam search (definition above): one wave per image over the rows'
+// k finalists each in cand_v / cand_i [k_in * B][k], k_in = 1 (step 0: every group draws on beam 0) or k.
+// Group g's n = k' k (step 0: k) <= 128 entries sit two per lane; the tokens chosen so far (<= k - k' <= 15)
+// sit one per lane in `said`, lane q holding the q-th, and are read back by lane broadcasts -- no LDS, no
+// atomics.  Each of the k' rounds is beam_merge_wave's round on the penalised scores, with the unpenalised
+// score fetched from the winner's lane for out_prob.
+__global__ void __launch_bounds__(64) beam_group_merge_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
+                                                              int k_in, int B, int V, int k, int G, float lambda,
+                                                              float* __restrict__ out_prob, int32_t* __restrict__ out_src,
+                                                              int32_t* __restrict__ out_tok, BeamEnd e) {
+  const int i = blockIdx.x, lane = threadIdx.x, kg = k / G;
+  const int n = (k_in == 1 ? 1 : kg) * k;
+  int said = -1, n_said = 0;  // (n_said is the same in every lane)
+  for (int g = 0; g < G; ++g) {
+    const int j0 = k_in == 1 ? 0 : g * kg;
+    float v[2], p[2];
+    int c[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int en = lane + 64 * u;
+      v[u] = -INFINITY, c[u] = 0x7fffffff;
+      int tok = -1;  // the token a penalty looks at: none for an empty slot or a finished source
+      if (en < n) {
+        const int64_t r = (int64_t)(j0 + en / k) * B + i;
+        v[u] = cand_v[r * k + en % k], c[u] = cand_i[r * k + en % k];
+        if (c[u] != 0x7fffffff && !e.fin_src[r]) tok = c[u] % V;
+      }
+      int cnt = 0;  // (every lane runs the broadcasts)
+      for (int q = 0; q < n_said; ++q) cnt += __shfl(said, q, 64) == tok ? 1 : 0;
+      p[u] = __fsub_rn(v[u], __fmul_rn(lambda, (float)cnt));
+    }
+    for (int sel = 0; sel < kg; ++sel) {
+      float best = -INFINITY;
+      int bidx = 0x7fffffff, bpos = -1;
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+        if (p[u] > best || (p[u] == best && c[u] < bidx)) best = p[u], bidx = c[u], bpos = lane + 64 * u;
+      wave_best(best, bidx, bpos);
+      float mine = -INFINITY;
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+        if (bpos == lane + 64 * u) mine = v[u], p[u] = -INFINITY, c[u] = 0x7fffffff;
+      const bool none = bidx == 0x7fffffff;  // fewer than k' candidates
+      const float score = __shfl(mine, none ? 0 : bpos & 63, 64);  // (-inf where none)
+      if (!none && !e.fin_src[(bidx / V) * B + i]) {  // a live source's token counts against the later groups
+        if (lane == n_said) said = bidx % V;
+        ++n_said;
+      }
+      if (lane == 0) {
+        int src, tok;
+        beam_end_emit(e, g * kg + sel, i, B, V, score, bidx, out_prob, out_src, out_tok, src, tok);
+      }
+    }
+  }
 }
 
 template <int KM, bool ENDED = false>
@@ -693,6 +778,7 @@ __global__ void __launch_bounds__(1024) beam_slab_step_kernel(
 template <bool ENDED>
 static void beam_step_launch(const BeamStep& b, BeamEndArg<ENDED> ea, hipStream_t s) {
   const BeamReorder* ro = b.reorder;
+  const BeamGroups* gr = b.groups && b.groups->G > 1 ? b.groups : nullptr;
   const int k = b.k, k_in = b.k_in, B = b.B, V = b.V, rows = k_in * B, logsm = ENDED ? 1 : b.logsm;
   with_km(k, [&](auto km) {
     constexpr int KM = decltype(km)::value;
@@ -705,6 +791,14 @@ static void beam_step_launch(const BeamStep& b, BeamEndArg<ENDED> ea, hipStream_
                                                               b.cand_i);
     else beam_row_topk<KM, ENDED>(b.logits, b.prev, rows, B, V, k, logsm, b.cand_v, b.cand_i, s, ea);
   });
+  if constexpr (ENDED) {
+    if (gr) {
+      beam_group_merge_kernel<<<B, 64, 0, s>>>(b.cand_v, b.cand_i, k_in, B, V, k, gr->G, gr->lambda, b.out_prob,
+                                               b.out_src, b.out_tok, ea);
+      CAPGEN_HIP(hipGetLastError());
+      return;
+    }
+  }
   if (!ro) beam_merge_kernel<ENDED><<<B, 64, 0, s>>>(b.cand_v, b.cand_i, k_in, B, V, k, b.out_prob, b.out_src, b.out_tok, ea);
   CAPGEN_HIP(hipGetLastError());
 }
@@ -714,6 +808,15 @@ void beam_step(const BeamStep& b, hipStream_t s) {
   const BeamReorder* ro = b.reorder;
   const int k = b.k, k_in = b.k_in, V = b.V;
   require(k >= 1 && k <= 16 && k_in >= 1 && k_in * k <= 256, "beam_step: k in [1, 16], k_in * k in [1, 256]");
+  if (b.groups) {
+    require(b.groups->G >= 1 && b.groups->G <= k && k % b.groups->G == 0,
+            "beam_step: num_groups must be in [1, beam_size] and divide it");
+    require(b.groups->lambda >= 0.f && b.groups->lambda < INFINITY,
+            "beam_step: diversity_penalty must be finite and >= 0");  // (false for a NaN)
+  }
+  const BeamGroups* gr = b.groups && b.groups->G > 1 ? b.groups : nullptr;  // (one group: no groups)
+  require(!gr || (e && !b.stats && !ro), "beam_step: groups need end and take neither stats nor reorder");
+  require(!gr || k_in == 1 || k_in == k, "beam_step: k_in must be 1 or k with groups");
   require(!ro || b.stats, "beam_step: reorder without stats (the one-launch form selects from the slab stats)");
   require(!e || !b.stats || ro, "beam_step: end with stats but without reorder (no END-aware two-launch slab form)");
   require(!b.stats || slab_select_ok(V), "beam_step: V must be in [1, 16384] with stats");
@@ -734,9 +837,10 @@ void beam_step(const BeamStep& b, hipStream_t s) {
     else {
       op(s, "beam_row_topk_ended", {rd(b.logits, Rin * V * 4), rd(b.prev, b.prev ? Rin * 4 : 0), rd(n.fin_src, Rin * 4),
                                     wr(b.cand_v, Rin * k * 4), wr(b.cand_i, Rin * k * 4)});
-      op(s, "beam_merge_ended", {rd(b.cand_v, Rin * k * 4), rd(b.cand_i, Rin * k * 4), rd(n.fin_src, Rin * 4),
-                                 rd(n.len_src, Rin * 4), wr(b.out_prob, R * 4), wr(b.out_src, R * 4),
-                                 wr(b.out_tok, R * 4), wr(n.fin_dst, R * 4), wr(n.len_dst, R * 4)});
+      op(s, gr ? "beam_group_merge" : "beam_merge_ended",
+         {rd(b.cand_v, Rin * k * 4), rd(b.cand_i, Rin * k * 4), rd(n.fin_src, Rin * 4), rd(n.len_src, Rin * 4),
+          wr(b.out_prob, R * 4), wr(b.out_src, R * 4), wr(b.out_tok, R * 4), wr(n.fin_dst, R * 4),
+          wr(n.len_dst, R * 4)});
     }
   }
   if (e) beam_step_launch<true>(b, *e, s);

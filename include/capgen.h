@@ -219,6 +219,30 @@ int capgen_beam_nbest(capgen_t* h, const void* feats, int feats_dtype, const flo
                       int32_t* len_out,   /* [n_best*B], nullable */
                       void* stream);
 
+/* Diverse beam search (Vijayakumar et al. 2016): capgen_beam_nbest with the beam_size beams split into
+ * num_groups groups of k' = beam_size / num_groups, group g being beams g k' .. (g + 1) k' - 1.  At every
+ * position the groups of an image are served in order; group g selects its k' best among its own k' source
+ * rows' candidates (at step 0: beam 0's), a live source's candidate for word v scored logp + log-softmax[v] -
+ * diversity_penalty * c(v), c(v) = the hypotheses the earlier groups selected at this position from a live
+ * source with word v (<END> counts like any word); a finished source offers itself once, unpenalised.  The
+ * penalty only orders candidates: logp stays the sum of the model's token log-probabilities.  At the end each
+ * group returns its n_best by logp / max(len, 1)^length_penalty: output row (g * n_best + rank) * B + b.
+ * num_groups = 1 is capgen_beam_nbest bit for bit (the same launches) whatever diversity_penalty;
+ * diversity_penalty = 0 gives num_groups identical groups.  Decode constraints apply as to capgen_beam_nbest.
+ * Either dtype selects with the full-row top-k, one group-merge launch and the three reorder launches per
+ * token.  Definition: csrc/select.hip.
+ * num_groups in [1, beam_size] and dividing it, diversity_penalty finite and >= 0, n_best in
+ * [1, beam_size / num_groups], the rest as capgen_beam_nbest.
+ * Added without a change of CAPGEN_ABI_VERSION: no existing entry changed (backward compatible). */
+int capgen_beam_diverse(capgen_t* h, const void* feats, int feats_dtype, const float* pos, int B, int N,
+                        int beam_size, int num_groups, float diversity_penalty, int end_id, float length_penalty,
+                        int n_best,
+                        int64_t* ids_out,   /* [num_groups*n_best*B, max_length], group-major */
+                        float* score_out,   /* [num_groups*n_best*B], nullable */
+                        float* logp_out,    /* [num_groups*n_best*B], nullable */
+                        int32_t* len_out,   /* [num_groups*n_best*B], nullable */
+                        void* stream);
+
 /* Sampled decoding: n_samples captions per image drawn from the model's distribution, one encoder
  * pass, KV-cached.  Position t draws token ~ softmax(logits / temperature) restricted to the top_k
  * largest logits (top_k = 0: the whole vocabulary) by Gumbel-max over the counter hash of (seed,
@@ -299,6 +323,12 @@ int capgen_ensemble_beam_nbest(const capgen_ensemble* e, const void* feats, int 
 int capgen_ensemble_sample(const capgen_ensemble* e, const void* feats, int feats_dtype, const float* pos, int B, int N,
                            int n_samples, float temperature, int top_k, float top_p, uint64_t seed, int64_t* ids_out,
                            float* logp_out, void* stream);
+/* capgen_beam_diverse over the ensemble's distribution: its arguments after h.
+ * Added without a change of CAPGEN_ABI_VERSION: no existing entry changed (backward compatible). */
+int capgen_ensemble_beam_diverse(const capgen_ensemble* e, const void* feats, int feats_dtype, const float* pos, int B,
+                                 int N, int beam_size, int num_groups, float diversity_penalty, int end_id,
+                                 float length_penalty, int n_best, int64_t* ids_out, float* score_out,
+                                 float* logp_out, int32_t* len_out, void* stream);
 
 /* Decode scoring of capgen_greedy / capgen_beam: 0 (default) = Transformer (argmax of Softmax,
  * beams accumulate probabilities, model.py:124-128,183); 1 = PolicyNetwork, the SCST model
@@ -649,6 +679,13 @@ int capgen_debug_beam_step_ended(const float* logits, const void* stats, const f
                                  int32_t* out_tok, const int64_t* seq_src, int64_t* seq_dst, int Tw,
                                  const int32_t* ids_src, int32_t* ids_dst, const int32_t* kv_src, int32_t* kv_dst,
                                  int Tc, int t, void* stream);
+/* One step of capgen_beam_diverse's selection (definition: csrc/select.hip): the full-row END-aware top-k with
+ * k finalists per row, then the group merge.  k_in = 1 (step 0: every group draws on beam 0) or k; the other
+ * arguments as capgen_debug_beam_step_ended's full-row form.  num_groups = 1 launches that form itself. */
+int capgen_debug_beam_group_step(const float* logits, const float* prev, int k_in, int B, int V, int k,
+                                 int num_groups, float diversity_penalty, int end_id, const int32_t* fin_src,
+                                 const int32_t* len_src, int32_t* fin_dst, int32_t* len_dst, float* cand_v,
+                                 int32_t* cand_i, float* out_prob, int32_t* out_src, int32_t* out_tok, void* stream);
 /* The end of capgen_beam_nbest: the n_best of the k hypotheses (rows j * B + i of seq [k * B][Tw], logp, len)
  * per image by logp / max(len, 1)^length_penalty -> ids_out [n_best * B][Tw], score / logp / len (nullable). */
 int capgen_debug_beam_finish(const int64_t* seq, const float* logp, const int32_t* len, int k, int B, int Tw,

@@ -15,6 +15,11 @@ ens2_beam5e / ens3_beam5e / ens2_sample1: beam5e / sample1 over an ensemble of 2
 weights of seeds 0, 1, 2; capgen.engine.ensemble_beam_nbest / ensemble_sample, equal weights, mode 'prob'): every
 member's decoder steps plus one ensemble_combine launch per step, read against K x the single-engine mode of the
 same run.
+beam6 / beam6g3: Engine.beam_nbest at beam 6 and diverse beam search (Engine.beam_diverse, beam 6 in 3 groups,
+diversity_penalty 0.5), both with <END> = id 2, length_penalty 0 and n_best 1 (per group): the same decoder steps;
+beam6g3 selects with the full-row top-k, the group merge and the three reorder launches per token where bf16
+beam6 takes one fused launch, so it is read against beam6 of the same run.  --dtype fp32 runs every mode on the
+fp32 engine.
 
 Algorithmic work (KV-cached count): beam-5 1776.7 GFLOP, greedy 699.4 GFLOP per
 256-image batch.  The reference CPU path (no KV cache) took 25.0 s (beam) / 5.87 s (greedy) per
@@ -37,6 +42,7 @@ from capgen.synthetic import synthetic_batch  # noqa: E402
 GFLOP = {"beam5": 1776.7, "greedy": 699.4, "sample1": 699.4, "sample5": 1776.7,  # (sampleN: its decode steps')
          "sample1p": 699.4, "sample5p": 1776.7, "beam5e": 1776.7, "beam5en": 1776.7,
          "beam5ec": 1776.7, "sample1c": 699.4,
+         "beam6": 2046.0, "beam6g3": 2046.0,  # (beam5 + one more row's decoder steps: (1776.7 - 699.4) / 4)
          "ens2_beam5e": 2 * 1776.7, "ens3_beam5e": 3 * 1776.7, "ens2_sample1": 2 * 699.4}  # (every member's steps)
 
 
@@ -46,9 +52,10 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1, help="untimed calls first (the first one tunes GEMM shapes and sizes the workspaces)")
     ap.add_argument("--modes", default="beam5,greedy", help="of beam5, greedy, sample1, sample5, sample1p, sample5p, beam5e, beam5en, beam5ec, sample1c, "
-                    "ens2_beam5e, ens3_beam5e, ens2_sample1")
+                    "ens2_beam5e, ens3_beam5e, ens2_sample1, beam6, beam6g3")
+    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp32"))
     args = ap.parse_args()
-    cfg = preset("C2", dtype="bf16")
+    cfg = preset("C2", dtype=args.dtype)
     dev = torch.device("cuda", 0)
     eng = Engine(cfg, dev)
     eng.load_state_dict({k: torch.from_numpy(v) for k, v in reference_init_state_dict(cfg, seed=0).items()})
@@ -67,7 +74,7 @@ def main():
     B, N = args.batch, 36
     f, p, _ = synthetic_batch(B, N, cfg.encode_dim_features, cfg.encode_dim_positions, cfg.max_length,
                               cfg.num_vocab, seed=7)
-    f = f.to(dev, torch.bfloat16).contiguous()
+    f = f.to(dev, torch.bfloat16 if args.dtype == "bf16" else torch.float32).contiguous()
     p = p.to(dev).contiguous()
     runs = {"beam5": lambda: eng.beam(f, p, 5), "greedy": lambda: eng.greedy(f, p, want_attention=False),
             "sample1": lambda: eng.sample(f, p, n_samples=1, seed=1), "sample5": lambda: eng.sample(f, p, n_samples=5, seed=1),
@@ -77,6 +84,8 @@ def main():
             "beam5en": lambda: eng.beam_nbest(f, p, 5, 2, length_penalty=1.0, n_best=5),
             "beam5ec": lambda: eng.beam_nbest(f, p, 5, 2, length_penalty=0.0, n_best=1),
             "sample1c": lambda: eng.sample(f, p, n_samples=1, seed=1),
+            "beam6": lambda: eng.beam_nbest(f, p, 6, 2, length_penalty=0.0, n_best=1),
+            "beam6g3": lambda: eng.beam_diverse(f, p, 6, 3, 0.5, 2, length_penalty=0.0, n_best=1),
             "ens2_beam5e": lambda: ensemble_beam_nbest(ensemble(2), f, p, 5, 2, length_penalty=0.0, n_best=1),
             "ens3_beam5e": lambda: ensemble_beam_nbest(ensemble(3), f, p, 5, 2, length_penalty=0.0, n_best=1),
             "ens2_sample1": lambda: ensemble_sample(ensemble(2), f, p, n_samples=1, seed=1)}
@@ -97,7 +106,7 @@ def main():
         dt = (time.perf_counter() - t0) / args.reps
         print(json.dumps({"metric": f"generate {name} images/sec (C4: B={B}, max_length={cfg.max_length})",
                           "value": round(B / dt, 1), "unit": "images/s", "ms_per_batch": round(dt * 1e3, 3),
-                          "achieved_tflops": round(GFLOP[name] * (B / 256) / dt / 1e3, 2), "dtype": "bf16",
+                          "achieved_tflops": round(GFLOP[name] * (B / 256) / dt / 1e3, 2), "dtype": args.dtype,
                           "data": "synthetic", "gemm_shapes_tuned_live": _lib.tune_live_count()}), flush=True)
 
 
