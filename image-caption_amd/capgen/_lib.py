@@ -146,6 +146,12 @@ _SIGS = {
                                                C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P]),
     "capgen_debug_beam_group_step": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                                _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "capgen_beam_forced": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P, _P,
+                                     C.c_int, _P, _P, _P, _P, _P, _P]),
+    "capgen_ensemble_beam_forced": (C.c_int, [C.POINTER(capgen_ensemble), _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_float, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "capgen_debug_beam_forced_step": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int,
+                                                _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "capgen_sample": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, _P, _P,
                                 _P]),
     "capgen_sample_nucleus": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,

@@ -74,6 +74,82 @@ def check_diverse_call(beam_size, num_groups, diversity_penalty, end_id, length_
     return True
 
 
+def check_beam_forced_args(beam_size, end_id, length_penalty, n_best, word, group, B, num_vocab):
+    """The argument rules of capgen_beam_forced, as check_beam_nbest_args, and those of its word / group slots
+    (integer arrays [B, W]; word -1: an empty slot), which the library cannot check: it never reads the device
+    arrays on the host.  Returns (beam_size, n_best, word, group) with word / group as int32 arrays, or None
+    for both where no slot holds a word -- the call is then beam_nbest's."""
+    try:
+        beam_size, n_best = check_beam_nbest_args(beam_size, end_id, length_penalty, n_best, num_vocab)
+    except (TypeError, ValueError) as e:
+        raise type(e)(str(e).replace("beam_nbest", "beam_forced")) from None
+    word, group = np.asarray(word), np.asarray(group)
+    for name, a in (("word", word), ("group", group)):
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise TypeError(f"capgen beam_forced: {name} must hold integers, not {a.dtype}")
+    if word.ndim != 2 or word.shape[0] != B:
+        raise ValueError(f"capgen beam_forced: word must be [B = {B}, W], not {list(word.shape)}")
+    if group.shape != word.shape:
+        raise ValueError(f"capgen beam_forced: group must have word's shape {list(word.shape)}, not {list(group.shape)}")
+    held = word != -1
+    if not held.any():
+        return beam_size, n_best, None, None
+    W = word.shape[1]
+    if beam_size + W > 15:
+        raise ValueError(f"capgen beam_forced: beam_size + words must be <= 15, not {beam_size} + {W}")
+    if beam_size + W + 1 > num_vocab:
+        raise ValueError(f"capgen beam_forced: beam_size + words + 1 must be <= num_vocab, not {beam_size} + {W} + 1")
+    bad = held & ((word < 0) | (word >= num_vocab) | (word == end_id) | (word == 0) | (word == 1))
+    if bad.any():
+        raise ValueError(f"capgen beam_forced: word must be -1 or in [0, num_vocab) and not end_id, 0 (<NULL>) or 1 "
+                         f"(<START>), not {int(word[bad][0])}")
+    if ((group < 0) | (group >= 16))[held].any():
+        raise ValueError(f"capgen beam_forced: group must be in [0, 16), not {int(group[held & ((group < 0) | (group >= 16))][0])}")
+    return beam_size, n_best, np.ascontiguousarray(word, np.int32), np.ascontiguousarray(group, np.int32)
+
+
+def must_include_slots(must_include, word_to_idx, B, beam_size, num_groups=1):
+    """beam_captions' must_include -> (word, group) int arrays [B, W] for beam_forced, or None where nothing is
+    required (None, or every entry empty: the call stays what it was).  must_include has one entry per image,
+    each a sequence of groups, each group a word or a sequence of alternative words.  A ValueError names
+    must_include and what is wrong with it, before the library is called."""
+    if must_include is None:
+        return None
+    per_image = list(must_include)
+    if len(per_image) != B:
+        raise ValueError(f"must_include must have one entry per image ({B}), not {len(per_image)}")
+    slots = []
+    for i, entry in enumerate(per_image):
+        if isinstance(entry, str):
+            raise ValueError(f"must_include[{i}] must be a sequence of groups, not the string {entry!r} "
+                             f"(write [{entry!r}] for one required word)")
+        groups = [] if entry is None else list(entry)
+        if len(groups) > 16:
+            raise ValueError(f"must_include[{i}]: at most 16 groups per image, not {len(groups)}")
+        mine = []
+        for g, alt in enumerate(groups):
+            for w in ([alt] if isinstance(alt, str) else list(alt)):
+                if w not in word_to_idx:
+                    raise ValueError(f"must_include[{i}]: unknown word {w!r}")
+                if w in ("<END>", "<NULL>", "<START>"):
+                    raise ValueError(f"must_include[{i}]: {w} cannot be required")
+                mine.append((int(word_to_idx[w]), g))
+        slots.append(mine)
+    W = max(len(s) for s in slots) if slots else 0
+    if W == 0:
+        return None
+    if not isinstance(num_groups, bool) and isinstance(num_groups, (int, np.integer)) and num_groups > 1:
+        raise ValueError("must_include cannot be combined with num_groups > 1")
+    if isinstance(beam_size, (int, np.integer)) and beam_size + W > 15:
+        raise ValueError(f"must_include: too many words for the beam: beam_size + words must be <= 15, not "
+                         f"{beam_size} + {W}")
+    word, group = np.full((B, W), -1, np.int32), np.zeros((B, W), np.int32)
+    for i, mine in enumerate(slots):
+        for s, (w, g) in enumerate(mine):
+            word[i, s], group[i, s] = w, g
+    return word, group
+
+
 def check_ema_decay(decay) -> float:
     """Engine.set_ema's argument rule, on the f32 the engine stores (0.99999999 rounds to 1.0f): the value
     to pass on, 0.0 for off; a ValueError naming the argument otherwise."""
@@ -140,6 +216,31 @@ def _beam_diverse(lead, call, feats, pos, beam_size, num_groups, diversity_penal
     return ids.view(n, B, T), score.view(n, B), logp.view(n, B), length.view(n, B)
 
 
+def _beam_forced(lead, call, feats, pos, beam_size, end_id, word, group, length_penalty, n_best):
+    """Engine.beam_forced and ensemble_beam_forced, as _beam_nbest, plus met [n_best, B] int32"""
+    f, ft, p, _ = lead._inputs(feats, pos)
+    B, N, _ = f.shape
+    if isinstance(word, torch.Tensor):
+        word = word.cpu().numpy()
+    if isinstance(group, torch.Tensor):
+        group = group.cpu().numpy()
+    beam_size, n, word, group = check_beam_forced_args(beam_size, end_id, length_penalty, n_best, word, group, B,
+                                                       lead.cfg.num_vocab)
+    T = lead.cfg.max_length
+    dev = lead.device
+    W = 0 if word is None else word.shape[1]
+    wd = None if word is None else torch.from_numpy(word).to(dev)
+    gd = None if group is None else torch.from_numpy(group).to(dev)
+    ids = torch.empty(n * B, T, dtype=torch.int64, device=dev)
+    score = torch.empty(n * B, dtype=torch.float32, device=dev)
+    logp = torch.empty(n * B, dtype=torch.float32, device=dev)
+    length = torch.empty(n * B, dtype=torch.int32, device=dev)
+    met = torch.empty(n * B, dtype=torch.int32, device=dev)
+    _lib.check(call(_ptr(f), ft, _ptr(p), B, N, beam_size, int(end_id), float(length_penalty), n, _ptr(wd), _ptr(gd),
+                    W, _ptr(ids), _ptr(score), _ptr(logp), _ptr(length), _ptr(met), _stream(dev)))
+    return ids.view(n, B, T), score.view(n, B), logp.view(n, B), length.view(n, B), met.view(n, B)
+
+
 def _sample(lead, call, feats, pos, n_samples, temperature, top_k, seed, want_logp, top_p):
     """Engine.sample and ensemble_sample, as _beam_nbest"""
     f, ft, p, _ = lead._inputs(feats, pos)
@@ -175,6 +276,16 @@ def ensemble_beam_diverse(engines, feats, pos, beam_size, num_groups, diversity_
     lead, e = engines[0], _lib.ensemble([x.h for x in engines], weights, m)
     return _beam_diverse(lead, lambda *a: lead.lib.capgen_ensemble_beam_diverse(C.byref(e), *a), feats, pos,
                          beam_size, num_groups, diversity_penalty, end_id, length_penalty, n_best)
+
+
+def ensemble_beam_forced(engines, feats, pos, beam_size, end_id, word, group, length_penalty=0.0, n_best=1,
+                         weights=None, mode="prob"):
+    """Engine.beam_forced over the averaged next-word distribution of several engines
+    (capgen_ensemble_beam_forced; members, weights and mode as ensemble_beam_nbest's)."""
+    engines, weights, m = check_ensemble_args(engines, weights, mode)
+    lead, e = engines[0], _lib.ensemble([x.h for x in engines], weights, m)
+    return _beam_forced(lead, lambda *a: lead.lib.capgen_ensemble_beam_forced(C.byref(e), *a), feats, pos, beam_size,
+                        end_id, word, group, length_penalty, n_best)
 
 
 def ensemble_sample(engines, feats, pos, n_samples=1, temperature=1.0, top_k=0, seed=0, want_logp=True, top_p=1.0,
@@ -603,6 +714,18 @@ class Engine:
         beam_nbest."""
         return _beam_diverse(self, lambda *a: self.lib.capgen_beam_diverse(self.h, *a), feats, pos, beam_size,
                              num_groups, diversity_penalty, end_id, length_penalty, n_best)
+
+    def beam_forced(self, feats, pos, beam_size, end_id, word, group, length_penalty=0.0, n_best=1):
+        """Forced-word beam search (capgen_beam_forced): beam_nbest over captions that must contain given words.
+        word / group: integer arrays [B, W], image i's slots (word -1: empty); a group in [0, 16) is a set of
+        alternatives, met once the caption holds any of them; beam_size + W <= 15.  The search keeps, per
+        position, the best hypotheses of every count of met groups in turn (highest count first) and never lets
+        a hypothesis end with a group unmet; logp is the model's log-probability, nothing added.  Returns (ids
+        [n_best, B, max_length] int64, score, logp f32, len and met int32 [n_best, B]), ordered by (groups met
+        descending, score descending); met is the bitmask of the groups each caption met -- one that ran out of
+        positions may miss some.  No word on any image is beam_nbest bit for bit, met all zero."""
+        return _beam_forced(self, lambda *a: self.lib.capgen_beam_forced(self.h, *a), feats, pos, beam_size, end_id,
+                            word, group, length_penalty, n_best)
 
     def set_decode_constraints(self, no_repeat_ngram=0, min_length=0, end_id=-1, repetition_penalty=1.0, banned=()):
         """What beam_nbest and sample may not say, from now on (capgen_set_decode_constraints; greedy and beam

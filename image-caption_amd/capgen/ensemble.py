@@ -9,7 +9,8 @@ import math
 
 import torch
 
-from .engine import check_diverse_call, check_ensemble_args, ensemble_beam_diverse, ensemble_beam_nbest, ensemble_sample
+from .engine import (check_diverse_call, check_ensemble_args, ensemble_beam_diverse, ensemble_beam_forced,
+                     ensemble_beam_nbest, ensemble_sample, must_include_slots)
 from .utils import sequence_logprob
 
 
@@ -38,15 +39,22 @@ class Ensemble:
 
     def beam_captions(self, object_features, position_features, beam_size, length_penalty=0.0, n_best=1,
                       no_repeat_ngram=0, min_length=0, repetition_penalty=1.0, banned_words=(), num_groups=1,
-                      diversity_penalty=0.0):
-        """MODEL.beam_captions over the ensemble distribution: (captions, score), the same shapes (num_groups
-        and diversity_penalty included); the constraints are the leader's, for this call only."""
+                      diversity_penalty=0.0, must_include=None):
+        """MODEL.beam_captions over the ensemble distribution: (captions, score), the same shapes (num_groups,
+        diversity_penalty and must_include included); the constraints are the leader's, for this call only."""
         lead = self.leader
         end = -1 if lead.end_idx is None else int(lead.end_idx)
+        slots = None if must_include is None else must_include_slots(must_include, lead.word_to_idx,
+                                                                      len(object_features), beam_size, num_groups)
         diverse = check_diverse_call(beam_size, num_groups, diversity_penalty, end, length_penalty, n_best,
                                      lead.config.num_vocab)
         with lead._constrained(no_repeat_ngram, min_length, repetition_penalty, banned_words):
-            if diverse:
+            if slots is not None:
+                ids, score, _, _, _ = ensemble_beam_forced(self._engines(), object_features, position_features,
+                                                           beam_size, end, slots[0], slots[1],
+                                                           length_penalty=length_penalty, n_best=n_best,
+                                                           weights=self.weights, mode=self.mode)
+            elif diverse:
                 ids, score, _, _ = ensemble_beam_diverse(self._engines(), object_features, position_features,
                                                          beam_size, num_groups, diversity_penalty, end,
                                                          length_penalty=length_penalty, n_best=n_best,

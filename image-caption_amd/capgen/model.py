@@ -134,6 +134,14 @@ class Transformer:
         return self.engine.beam_diverse(object_features, position_features, beam_size, num_groups,
                                         diversity_penalty, end_id, length_penalty=length_penalty, n_best=n_best)
 
+    def beam_search_forced(self, object_features, position_features, beam_size, end_id, word, group,
+                           length_penalty=0.0, n_best=1):
+        """Forced-word beam search (constrained beam search, Anderson et al. 2017): beam_search_nbest over captions
+        that must contain a word of every group in word / group ([B, W] slots, -1: empty).  Returns (ids, score,
+        logp, len, met) -- Engine.beam_forced."""
+        return self.engine.beam_forced(object_features, position_features, beam_size, end_id, word, group,
+                                       length_penalty=length_penalty, n_best=n_best)
+
     def sample_caption_vector(self, object_features, position_features, n_samples=1, temperature=1.0, top_k=0,
                               seed=None, top_p=1.0):
         """n_samples captions per image drawn from the model's distribution (temperature / top-k /

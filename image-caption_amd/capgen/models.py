@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from .config import CapgenConfig
-from .engine import check_diverse_call
+from .engine import check_diverse_call, must_include_slots
 from .model import PolicyNetwork, Transformer
 from .schedule import ScheduledSteps
 from .staging import HostBatchStager
@@ -82,7 +82,7 @@ class MODEL_init:
 
     def beam_captions(self, object_features, position_features, beam_size, length_penalty=0.0, n_best=1,
                       no_repeat_ngram=0, min_length=0, repetition_penalty=1.0, banned_words=(), num_groups=1,
-                      diversity_penalty=0.0):
+                      diversity_penalty=0.0, must_include=None):
         """The n_best captions per image of a beam search that stops at <END> (generate_caption keeps the
         reference's search, which does not): (captions, score) -- n_best lists of B strings, best first, and
         their scores [n_best, B] (f32, on the model's device): the caption's log-probability through <END>
@@ -94,12 +94,24 @@ class MODEL_init:
         num_groups > 1: diverse beam search -- the beams in num_groups groups, a later group penalised by
         diversity_penalty for each earlier hypothesis that chose the same word at the same position; n_best
         then counts per group (<= beam_size / num_groups) and num_groups * n_best lists come back, group-major
-        (all of group 0's first), with scores [num_groups * n_best, B] that never contain the penalty."""
+        (all of group 0's first), with scores [num_groups * n_best, B] that never contain the penalty.
+        must_include: words the captions must contain (forced-word beam search, Engine.beam_forced) -- one entry
+        per image, each a sequence of groups, each group a word or a sequence of alternative words ("dog", or
+        ("dog", "dogs", "puppy")); an empty entry requires nothing of its image.  The captions come back ordered
+        by the number of groups they contain, then by score; a caption that ran out of positions may miss a
+        group.  At most 16 groups per image and beam_size + (the most words of any image) <= 15; not together
+        with num_groups > 1.  None, or every entry empty, is the call as it was."""
         end = -1 if self.end_idx is None else int(self.end_idx)
+        slots = None if must_include is None else must_include_slots(must_include, self.word_to_idx,
+                                                                      len(object_features), beam_size, num_groups)
         diverse = check_diverse_call(beam_size, num_groups, diversity_penalty, end, length_penalty, n_best,
                                      self.config.num_vocab)
         with self._constrained(no_repeat_ngram, min_length, repetition_penalty, banned_words):
-            if diverse:
+            if slots is not None:
+                ids, score, _, _, _ = self.model.beam_search_forced(
+                    object_features=object_features, position_features=position_features, beam_size=beam_size,
+                    end_id=end, word=slots[0], group=slots[1], length_penalty=length_penalty, n_best=n_best)
+            elif diverse:
                 ids, score, _, _ = self.model.beam_search_diverse(
                     object_features=object_features, position_features=position_features, beam_size=beam_size,
                     num_groups=num_groups, diversity_penalty=diversity_penalty, end_id=end,

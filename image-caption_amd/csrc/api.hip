@@ -346,6 +346,16 @@ int capgen_beam_diverse(capgen_t* h, const void* feats, int ft, const float* pos
   });
 }
 
+int capgen_beam_forced(capgen_t* h, const void* feats, int ft, const float* pos, int B, int N, int k, int end_id,
+                       float length_penalty, int n_best, const int32_t* word, const int32_t* group, int W,
+                       int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, int32_t* met_out,
+                       void* stream) {
+  return decode_call(h, stream, [&] {
+    h->beam_forced(feats, dt(ft), pos, B, N, k, end_id, length_penalty, n_best, word, group, W, ids_out, score_out,
+                   logp_out, len_out, met_out, h->es);
+  });
+}
+
 int capgen_sample(capgen_t* h, const void* feats, int ft, const float* pos, int B, int N, int n_samples,
                   float temperature, int top_k, uint64_t sd, int64_t* ids_out, float* logp_out, void* stream) {
   return capgen_sample_nucleus(h, feats, ft, pos, B, N, n_samples, temperature, top_k, 1.f, sd, ids_out, logp_out,
@@ -376,6 +386,16 @@ int capgen_ensemble_beam_diverse(const capgen_ensemble* e, const void* feats, in
   return ensemble_call(e, "ensemble_beam_diverse", stream, [&](capgen_engine* h, const EnsembleRun& run) {
     h->beam_diverse(feats, dt(ft), pos, B, N, k, num_groups, diversity_penalty, end_id, length_penalty, n_best, ids_out,
                     score_out, logp_out, len_out, h->es, &run);
+  });
+}
+
+int capgen_ensemble_beam_forced(const capgen_ensemble* e, const void* feats, int ft, const float* pos, int B, int N,
+                                int k, int end_id, float length_penalty, int n_best, const int32_t* word,
+                                const int32_t* group, int W, int64_t* ids_out, float* score_out, float* logp_out,
+                                int32_t* len_out, int32_t* met_out, void* stream) {
+  return ensemble_call(e, "ensemble_beam_forced", stream, [&](capgen_engine* h, const EnsembleRun& run) {
+    h->beam_forced(feats, dt(ft), pos, B, N, k, end_id, length_penalty, n_best, word, group, W, ids_out, score_out,
+                   logp_out, len_out, met_out, h->es, &run);
   });
 }
 

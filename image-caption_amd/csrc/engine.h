@@ -178,6 +178,10 @@ struct GenWS {
   float *bprob, *bprob2;
   int32_t *bsrc, *btok;
   int32_t *bfin, *bfin2, *blen, *blen2;  // beam_nbest: [R] finished flag and length of each hypothesis
+  // beam_forced: [R] met masks, and its own finalist scratch (each row's kf <= 16 finalists and W <= 14 word scores)
+  int32_t *bmet, *bmet2;
+  float* fcand_v;   // [R][32]
+  int32_t* fcand_i;  // [R][16]
 };
 
 // Ensemble decoding: a capgen_ensemble after its checks.  m[0] leads: the call runs on its stream, over its
@@ -929,8 +933,12 @@ struct capgen_engine {
   void beam_diverse(const void* feats, DType ft, const float* pos, int B, int N, int k, int G, float lambda, int end_id,
                     float alpha, int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out,
                     hipStream_t s, const EnsembleRun* ens = nullptr);
+  void beam_forced(const void* feats, DType ft, const float* pos, int B, int N, int k, int end_id, float alpha,
+                   int n_best, const int32_t* word, const int32_t* group, int W, int64_t* ids_out, float* score_out,
+                   float* logp_out, int32_t* len_out, int32_t* met_out, hipStream_t s, const EnsembleRun* ens = nullptr);
   void beam_run(const void* feats, DType ft, const float* pos, int B, int N, int k, const int* end_id, hipStream_t s,
-                const EnsembleRun* ens = nullptr, const BeamGroups* groups = nullptr);
+                const EnsembleRun* ens = nullptr, const BeamGroups* groups = nullptr,
+                const BeamForced* forced = nullptr);
   void sample(const void* feats, DType ft, const float* pos, int B, int N, int n, float temperature, int top_k,
               float top_p, uint64_t sd, int64_t* ids_out, float* logp_out, hipStream_t s,
               const EnsembleRun* ens = nullptr);

@@ -83,6 +83,10 @@ void capgen_engine::plan_gen(Planner& p, int R, int N) {
   p.take(g.bfin2, R);
   p.take(g.blen, R);
   p.take(g.blen2, R);
+  p.take(g.bmet, R);  // (beam_forced's, behind everything else: no other array moves)
+  p.take(g.bmet2, R);
+  p.take(g.fcand_v, (size_t)R * 32);
+  p.take(g.fcand_i, (size_t)R * 16);
 }
 
 void capgen_engine::ensure_gen(int R, int N) {
@@ -286,12 +290,45 @@ void capgen_engine::beam_diverse(const void* feats, DType ft, const float* pos, 
                 logp_out ? logp_out + h * out : nullptr, len_out ? len_out + h * out : nullptr, s);
 }
 
+// Forced-word beam search (definition: select.hip): beam_nbest's search in banks by the number of word groups a
+// hypothesis has met, word / group the images' W slots (device int32 [B][W]).  beam_run's loop with the full-row
+// END-aware top-k (kf = min(16, k + W + 1) finalists and the W slot words' scores per row), the bank merge and
+// the three reorder launches per token in either dtype (no fused slab form), then beam_finish with the bank key.
+// W = 0 (no slots: word / group unread) is beam_nbest itself, fused slab step included, with met_out zeroed.
+void capgen_engine::beam_forced(const void* feats, DType ft, const float* pos, int B, int N, int k, int end_id, float alpha,
+    int n_best, const int32_t* word, const int32_t* group, int W, int64_t* ids_out, float* score_out, float* logp_out,
+    int32_t* len_out, int32_t* met_out, hipStream_t s, const EnsembleRun* ens) {
+  require(k >= 1 && k <= 16 && k <= L.V, "beam_forced: beam_size must be in [1, min(16, num_vocab)]");
+  require(W >= 0, "beam_forced: words must be >= 0");
+  require(W == 0 || k + W <= 15, "beam_forced: beam_size + words must be <= 15");
+  require(W == 0 || k + W + 1 <= L.V, "beam_forced: beam_size + words + 1 must be <= num_vocab");
+  require(W == 0 || (word && group), "beam_forced: null word / group");
+  require(n_best >= 1 && n_best <= k, "beam_forced: n_best must be in [1, beam_size]");
+  require(end_id >= -1 && end_id < L.V, "beam_forced: end_id must be in [-1, num_vocab)");
+  require(alpha >= 0.f && alpha < INFINITY, "beam_forced: length_penalty must be finite and >= 0");  // (false for a NaN)
+  require(N >= 1 && N <= 64, "beam_forced: N must be in [1, 64]");
+  require(B >= 1, "beam_forced: need B >= 1");
+  require(ids_out != nullptr, "beam_forced: null ids_out");
+  require(dc.min_length == 0 || dc.end_id == end_id,
+          "beam_forced: end_id differs from the end_id of the decode constraints' min_length");
+  if (W == 0) {
+    beam_nbest(feats, ft, pos, B, N, k, end_id, alpha, n_best, ids_out, score_out, logp_out, len_out, s, ens);
+    if (met_out) memset_async(met_out, sizeof(int32_t) * n_best * B, s);
+    return;
+  }
+  const BeamForced forced{word, group, W, nullptr, nullptr};  // (met: beam_run's double buffer)
+  beam_run(feats, ft, pos, B, N, k, &end_id, s, ens, nullptr, &forced);
+  beam_finish(g.seq, g.bprob, g.blen, k, B, L.maxlen, alpha, n_best, ids_out, score_out, logp_out, len_out, s, g.bmet,
+              met_out);
+}
+
 // The loop of beam (end_id == nullptr: the reference's search, model.py:135-200) and of beam_nbest: leaves
 // the k * B hypotheses in g.seq, their scores in g.bprob and, for beam_nbest, g.bfin / g.blen.
 // ens (null: none): every step's logits are the ensemble's (ensemble_step below), nothing else changes.
 // groups (null: none; needs end_id): beam_diverse's selection, the hypotheses left group by group.
+// forced (null: none; needs end_id; its met pointers are ignored): beam_forced's selection, met left in g.bmet.
 void capgen_engine::beam_run(const void* feats, DType ft, const float* pos, int B, int N, int k, const int* end_id, hipStream_t s,
-    const EnsembleRun* ens, const BeamGroups* groups) {
+    const EnsembleRun* ens, const BeamGroups* groups, const BeamForced* forced) {
   const int R = k * B, Tc = L.maxlen, Tw = L.maxlen;
   if (ens) ensemble_begin(*ens, feats, ft, pos, B, N, R, s);
   else begin_decode(feats, ft, pos, B, N, R, s);
@@ -307,15 +344,19 @@ void capgen_engine::beam_run(const void* feats, DType ft, const float* pos, int 
   // (CAPGEN_FUSED_BEAM_STEP=0 restores the top-k, merge and three reorder launches); off that form the
   // END-aware step takes the full-row kernel, which reads the f32 logits of either dtype
   // (groups: the full-row top-k and the group merge; no fused form)
-  const bool fused_step = slab_decode() && fused_beam_step_on && k <= 16 && Tw == Tc && !groups;
+  // (forced: the full-row top-k and the bank merge; no fused form)
+  const bool fused_step = slab_decode() && fused_beam_step_on && k <= 16 && Tw == Tc && !groups && !forced;
   if (end_id) {  // every hypothesis starts live with no tokens
     memset_async(g.bfin, sizeof(int32_t) * R, s);
     memset_async(g.blen, sizeof(int32_t) * R, s);
   }
+  if (forced) memset_async(g.bmet, sizeof(int32_t) * R, s);  // no group met
   BeamStep b;  // what no step changes; the double-buffered arrays are set per step
   b.logits = g.logits, b.B = B, b.V = L.V, b.k = k, b.logsm = decode_logsm;
   b.stats = fused_step || (slab_decode() && !end_id) ? g.dstats : nullptr;
   b.cand_v = g.cand_v, b.cand_i = g.cand_i, b.out_src = g.bsrc, b.out_tok = g.btok, b.groups = groups;
+  BeamForced fo{};  // (met: set per step, double-buffered like fin / len)
+  if (forced) fo = *forced, b.forced = &fo, b.cand_v = g.fcand_v, b.cand_i = g.fcand_i;
   // The selection of position t over the k_in live beams per image with scores prev, and the reorder
   // behind it.  The K/V cache is never copied: row r writes its position-t K/V at [l][r][t] and reads
   // position j of its history from row kvrow[r][j] (the beam it descended from there); a reorder
@@ -328,7 +369,9 @@ void capgen_engine::beam_run(const void* feats, DType ft, const float* pos, int 
     ro.kv_src = g.kvrow, ro.kv_dst = g.kvrow2, ro.Tw = Tw, ro.Tc = Tc, ro.t = t;
     b.prev = prev, b.k_in = k_in, b.out_prob = g.bprob2;
     b.end = end_id ? &ended : nullptr, b.reorder = fused_step ? &ro : nullptr;
+    if (forced) fo.met_src = g.bmet, fo.met_dst = g.bmet2;
     beam_step(b, s);
+    if (forced) std::swap(g.bmet, g.bmet2);
     std::swap(g.bprob, g.bprob2);
     if (end_id) std::swap(g.bfin, g.bfin2), std::swap(g.blen, g.blen2);
     if (!fused_step) {

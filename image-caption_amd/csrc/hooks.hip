@@ -571,6 +571,33 @@ int capgen_debug_beam_group_step(const float* logits, const float* prev, int k_i
   });
 }
 
+int capgen_debug_beam_forced_step(const float* logits, const float* prev, int k_in, int B, int V, int k, int end_id,
+                                  const int32_t* word, const int32_t* group, int W, const int32_t* fin_src,
+                                  const int32_t* len_src, const int32_t* met_src, int32_t* fin_dst, int32_t* len_dst,
+                                  int32_t* met_dst, float* cand_v, int32_t* cand_i, float* out_prob, int32_t* out_src,
+                                  int32_t* out_tok, void* stream) {
+  return guarded([&] {
+    require(W >= 0 && W <= 16, "debug_beam_forced_step: words must be in [0, 16]");
+    require(B >= 1 && k >= 1, "debug_beam_forced_step: B, k >= 1");
+    require(W == 0 || word, "debug_beam_forced_step: null word");
+    const hipStream_t s = (hipStream_t)stream;
+    bool any = false;  // a word on any image?  (the hook may wait for the device; the engine never reads the slots)
+    if (W > 0) {
+      std::vector<int32_t> host((size_t)B * W);
+      CAPGEN_HIP(hipStreamSynchronize(s));
+      CAPGEN_HIP(hipMemcpy(host.data(), word, sizeof(int32_t) * host.size(), hipMemcpyDeviceToHost));
+      for (int32_t w : host) any = any || w != -1;
+    }
+    const BeamEnd e{fin_src, len_src, fin_dst, len_dst, end_id};
+    const BeamForced fo{word, group, W, met_src, met_dst};
+    BeamStep b = debug_beam_step(logits, nullptr, prev, k_in, B, V, k, 1, out_prob, out_src, out_tok);
+    b.cand_v = cand_v, b.cand_i = cand_i, b.end = &e;
+    if (any) b.forced = &fo;
+    else if (met_dst) CAPGEN_HIP(hipMemsetAsync(met_dst, 0, sizeof(int32_t) * k * B, s));  // no word: the END-aware step itself
+    beam_step(b, s);
+  });
+}
+
 int capgen_debug_beam_finish(const int64_t* seq, const float* logp, const int32_t* len, int k, int B, int Tw,
                              float length_penalty, int n_best, int64_t* ids_out, float* score_out, float* logp_out,
                              int32_t* len_out, void* stream) {

@@ -57,21 +57,35 @@ struct BeamGroups {
   int G;
   float lambda;
 };
+// Forced-word beam search (beam_forced; definition: select.hip): image i has W slots (word[i * W + s],
+// group[i * W + s]), word = -1 an empty slot, group in [0, 16); met [rows] is each hypothesis' bitmask of the
+// groups it has met, read from met_src and written to met_dst like fin / len.  k + W <= 15, k + W + 1 <= V.
+struct BeamForced {
+  const int32_t* word;
+  const int32_t* group;
+  int W;
+  const int32_t* met_src;
+  int32_t* met_dst;
+};
 // One beam-search step (model.py:183-190): rows j * B + i (j < k_in) of logits [k_in * B][V]; per image i the
 // k best (prev[j * B + i] (null: 0) + softmax, or log-softmax with logsm, of row j * B + i at v) under (score
 // desc, j * V + v asc) -> out_prob / src / tok[sel * B + i].  k, k_in >= 1, k <= 16, k_in * k <= 256.
-// The four nullable members choose the kernels, and beam_step is the only place that knows how:
-//   end   stats  reorder  groups   launches
-//   null  null   null     null     beam_row_topk_kernel (the exact full-row softmax) + beam_merge_kernel
-//   null  set    null     null     slab_row_topk_kernel + beam_merge_kernel
-//   null  set    set      null     beam_slab_step_kernel: selection, merge and reorder in one launch per image
-//   set   null   null     null     beam_row_topk_kernel<ENDED> + beam_merge_kernel<ENDED>
-//   set   set    set      null     beam_slab_step_kernel<ENDED>
-//   set   null   null     set      beam_row_topk_kernel<ENDED> + beam_group_merge_kernel (k_in = 1 or k)
+// The five nullable members choose the kernels, and beam_step is the only place that knows how:
+//   end   stats  reorder  groups  forced   launches
+//   null  null   null     null    null     beam_row_topk_kernel (the exact full-row softmax) + beam_merge_kernel
+//   null  set    null     null    null     slab_row_topk_kernel + beam_merge_kernel
+//   null  set    set      null    null     beam_slab_step_kernel: selection, merge and reorder in one launch per image
+//   set   null   null     null    null     beam_row_topk_kernel<ENDED> + beam_merge_kernel<ENDED>
+//   set   set    set      null    null     beam_slab_step_kernel<ENDED>
+//   set   null   null     set     null     beam_row_topk_kernel<ENDED> + beam_group_merge_kernel (k_in = 1 or k)
+//   set   null   null     null    set      beam_row_topk_kernel<ENDED, FORCED> with kf = min(16, k + W + 1) finalists and
+//                                          the W forced-word scores per row + beam_forced_merge_kernel (k_in <= k)
 // Every other combination has no kernel and is refused.  groups with G = 1 is no groups at all: the step is
 // the null-groups row of the same end / stats / reorder, whatever lambda.  stats: the rows' slab stats (above; V <= 16384); the
 // one-launch form also needs k_in <= 16.  cand_v / cand_i: k_in * B * k scratch (each row's k finalists) of
 // the two-launch forms only.  With end set the step always scores with the log-softmax: logsm is ignored.
+// forced: cand_v is k_in * B * (kf + W) (row r: its kf finalists' scores, then its W forced-word scores) and
+// cand_i k_in * B * kf.
 struct BeamStep {
   const float* logits = nullptr;
   const float2* stats = nullptr;
@@ -82,13 +96,17 @@ struct BeamStep {
   const BeamEnd* end = nullptr;          // null: the reference step
   const BeamReorder* reorder = nullptr;  // null: selection only
   const BeamGroups* groups = nullptr;    // null: one group
+  const BeamForced* forced = nullptr;    // null: no forced words
 };
 void beam_step(const BeamStep& b, hipStream_t s);
 // the end of the search: score = logp (alpha == 0) or logp / max(len, 1)^alpha; per image the n_best of the
 // k hypotheses (rows j * B + i of seq [k * B][Tw], logp, len) under (score desc, beam asc) -> row
-// rank * B + i of ids_out [n_best * B][Tw], score_out, logp_out, len_out (the last three nullable)
+// rank * B + i of ids_out [n_best * B][Tw], score_out, logp_out, len_out (the last three nullable).
+// met (null: none; beam_forced's [k * B] bitmasks): the order is (popcount(met) desc, score desc, beam asc), and
+// met_out (nullable) [n_best * B] gets the chosen hypotheses' masks.
 void beam_finish(const int64_t* seq, const float* logp, const int32_t* len, int k, int B, int Tw, float alpha,
-                 int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, hipStream_t s);
+                 int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, hipStream_t s,
+                 const int32_t* met = nullptr, int32_t* met_out = nullptr);
 
 // Decode constraints (beam_nbest and sample; definition: select.hip): what a row may not say next, from its
 // own token history.  banned is a DEVICE array here (the C ABI's struct carries a host one).

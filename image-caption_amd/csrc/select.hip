@@ -127,6 +127,47 @@ void argmax_softmax(const float* logits, int B, int V, int64_t* ids_out, int64_t
 // beam_row_topk_kernel<ENDED> runs once over all k_in * B rows with k finalists per row, and
 // beam_group_merge_kernel, one wave per image, walks the groups in order over the group's rows' finalists.
 // The bound is tight: k = G = 16 with 16 equal rows takes each row's ranks 0 .. 15.
+//
+// ---- forced-word beam search (beam_forced; constrained beam search: Anderson et al. 2017, in the fixed-beam
+// form of Post & Vilar 2018 / Hu et al. 2019: banks by the number of constraints met) ----
+// Inputs.  Image i has W slots (word[i][s], group[i][s]), word = -1 for an empty slot.  A group is a set of
+// alternatives ("dog", "dogs", "puppy") and is met by a hypothesis once it has appended any of the group's
+// words.  bits_i(v) = the OR of 1 << group over the slots of image i that hold v, full_i = the OR over all of
+// the image's slots; a word may sit in several groups.
+// Hypothesis: beam_nbest's, plus met, a bitmask that starts at 0.  logp stays the f32 running sum of the model's
+// token log-probabilities: nothing is renormalised or added to it.
+// Candidates at a position, for image i:
+// - a finished source j offers exactly (logp_j, j * V + 0), with met' = met_j;
+// - a live source j offers (logp_j + logsoftmax(row_j)[v], j * V + v) with met' = met_j | bits_i(v) for every v,
+//   except that v == end_id is no candidate while met_j != full_i: a hypothesis cannot end with a group unmet.
+// The bank of a candidate is popcount(met'), its rank its position within its own bank under (score descending,
+// flat index ascending).
+// Selection.  The k first candidates under (rank ascending, bank descending) become beams 0 .. k - 1 in that
+// order: the best of the highest non-empty bank, the best of the next non-empty bank and so on down, then the
+// second-best of each, until k are taken.  Scores are never compared across banks.
+// Update: beam_nbest's, plus met = met'.  Fewer than k candidates: the slots left over are beam_nbest's (score
+// -inf, source 0's state copied, its met included).
+// Finish: per image the n_best of the k hypotheses under (popcount(met) descending, logp / max(len, 1)^alpha
+// descending, beam ascending), met returned with them.  There is no forcing near max_length: a hypothesis may
+// run out of positions with a group unmet; it then ranks behind every hypothesis that met more groups, and met
+// says so.
+// Decode constraints edit the logits in front of the selection, as for beam_nbest; a forced word they block
+// scores -inf like any blocked word.
+// Consequences: with no word on any image the search is beam_nbest bit for bit (and takes its launches);
+// score_captions of a returned caption gives its returned logp.
+// Limits: W >= 1, k + W <= 15, k + W + 1 <= V, group in [0, 16), word in [0, V) or -1 and not end_id, 0 (<NULL>)
+// or 1 (<START>); not combined with beam groups.  (The kernels take a slot whose word or group is out of range
+// as empty; what word may not be is the callers' rule.)
+// Why the limit makes the kernels exact.  Row j's candidates are of two classes: staying ones keep bank
+// popcount(met_j), advancing ones are the words of its unmet groups -- at most W per row, enumerated explicitly.
+// At most k staying candidates of a row are ever selected, and they lie among the row's k + W + 1 <= 16 best:
+// the only candidates that can precede them in the row are its advancing words and a filtered <END>.  So
+// beam_row_topk_kernel<ENDED, FORCED> runs with kf = min(16, k + W + 1) finalists per row and writes, behind
+// them, the W scores prev + (x[w] - max) - lse of the image's slot words from the mx / lse it holds, in its own
+// f32 arithmetic.  beam_forced_merge_kernel, one wave per image, drops from the finalists every entry that
+// advances its row and a filtered <END>, and adds the row's advancing words from those W scores (a word held by
+// several slots once, from its first slot): an advancing word's score always comes from this route, never from
+// the finalist list, so there is nothing to de-duplicate.  That gives k_in (kf + W) <= 240 entries per image.
 
 // lane 0 of a merge, slot sel of image i: the selected (score, flat index) -> outputs and the new state
 __device__ __forceinline__ void beam_end_emit(const BeamEnd& e, int sel, int i, int B, int V, float best, int bidx,
@@ -152,24 +193,34 @@ __device__ __forceinline__ void beam_end_finalists(const float* prev, int r, int
 
 // the last argument of a step kernel: the END-aware form's state, nothing in the reference form
 struct NoBeamEnd {};
-template <bool ENDED>
-using BeamEndArg = std::conditional_t<ENDED, BeamEnd, NoBeamEnd>;
+// the forced-word form's: the END-aware state plus the image's slots and the hypotheses' met masks
+struct BeamEndForced : BeamEnd {
+  BeamForced f;
+};
+template <bool ENDED, bool FORCED = false>
+using BeamEndArg = std::conditional_t<FORCED, BeamEndForced, std::conditional_t<ENDED, BeamEnd, NoBeamEnd>>;
 
 // NT threads per row (W = NT / 64 waves), NV values per thread in registers (V <= NT * NV)
 // ENDED: e.fin_src [rows] marks the finished source rows (see above) and logsm is 1; false: the reference step
-template <int KM, int NV, int NT = 256, bool ENDED = false>
+// FORCED (with ENDED; k is kf here): row r's scores take kf + W floats of cand_v -- behind its kf finalists the
+// score of each of its image's W slot words (-inf for an empty slot or a finished row)
+template <int KM, int NV, int NT = 256, bool ENDED = false, bool FORCED = false>
 __global__ void __launch_bounds__(NT) beam_row_topk_kernel(const float* __restrict__ logits,
                                                             const float* __restrict__ prev, int B, int V, int k,
                                                             int logsm, float* __restrict__ cand_v,
-                                                            int* __restrict__ cand_i, BeamEndArg<ENDED> e) {
+                                                            int* __restrict__ cand_i, BeamEndArg<ENDED, FORCED> e) {
   constexpr int W = NT / 64;
   __shared__ float sh[W];
   __shared__ float wv[W][16];
   __shared__ int wi[W][16];
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = r / B;
+  int vs = k;  // row stride of cand_v
+  if constexpr (FORCED) vs = k + e.f.W;
   if constexpr (ENDED) {
     if (e.fin_src[r]) {  // (the whole workgroup: no barrier is skipped by some threads only)
-      if (wave == 0) beam_end_finalists(prev, r, j, V, k, lane, cand_v + (int64_t)r * k, cand_i + (int64_t)r * k);
+      if (wave == 0) beam_end_finalists(prev, r, j, V, k, lane, cand_v + (int64_t)r * vs, cand_i + (int64_t)r * k);
+      if constexpr (FORCED)
+        if (tid < e.f.W) cand_v[(int64_t)r * vs + k + tid] = -INFINITY;
       return;
     }
   }
@@ -199,8 +250,16 @@ __global__ void __launch_bounds__(NT) beam_row_topk_kernel(const float* __restri
   __syncthreads();
   if (wave == 0)
     wave_merge_finalists<W>(wv, wi, k, lane, [&](int sel, float v, int i) {
-      if (lane == 0) cand_v[(int64_t)r * k + sel] = v, cand_i[(int64_t)r * k + sel] = i;
+      if (lane == 0) cand_v[(int64_t)r * vs + sel] = v, cand_i[(int64_t)r * k + sel] = i;
     });
+  if constexpr (FORCED) {  // the slot words' scores, as the pass above scores a column
+    if (tid < e.f.W) {
+      const int w = e.f.word[(int64_t)(r % B) * e.f.W + tid];
+      float p = -INFINITY;
+      if ((unsigned)w < (unsigned)V) p = ((logits[(int64_t)r * V + w] - mx) - lse) + add;
+      cand_v[(int64_t)r * vs + k + tid] = p;
+    }
+  }
 }
 
 // One wave, one image: the k best of its n = k_in * k row finalists (n <= 256; entry e = (row j = e / k,
@@ -310,16 +369,115 @@ __global__ void __launch_bounds__(64) beam_group_merge_kernel(const float* __res
   }
 }
 
-template <int KM, bool ENDED = false>
+// The bank round-robin of forced-word beam search (definition above): one wave per image over its k_in <= k
+// source rows' kf finalists (cand_v [k_in * B][kf + W], cand_i [k_in * B][kf]) and W slot-word scores each,
+// n = k_in (kf + W) <= 240 entries, four per lane.  Lane s < W holds slot s of the image and every lane reads
+// the slots back by lane broadcasts -- no LDS, no atomics.  An entry keeps its score, flat index, met' and bank,
+// or is empty: a finalist that advances its row or is a filtered <END>, a slot word that does not advance the
+// row, repeats an earlier slot's word or belongs to a finished row.  Then rounds over the non-empty banks from
+// the highest down, each one beam_merge_wave's round restricted to a bank, until k are taken.
+__global__ void __launch_bounds__(64) beam_forced_merge_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
+                                                               int k_in, int B, int V, int k, int kf,
+                                                               float* __restrict__ out_prob, int32_t* __restrict__ out_src,
+                                                               int32_t* __restrict__ out_tok, BeamEndForced e) {
+  constexpr int kNone = 0x7fffffff;
+  const int i = blockIdx.x, lane = threadIdx.x, W = e.f.W, S = kf + W, n = k_in * S;
+  const int32_t* word = e.f.word + (int64_t)i * W;
+  int sw = -1, sb = 0;  // lane s: slot s' word and group bit (an empty slot: -1, 0)
+  if (lane < W) {
+    const int w = word[lane], g = e.f.group[(int64_t)i * W + lane];
+    if ((unsigned)w < (unsigned)V && (unsigned)g < 16u) sw = w, sb = 1 << g;
+  }
+  int full = sb;
+  full |= lane_xchg<32>(full), full |= lane_xchg<16>(full), full |= lane_xchg<8>(full);
+  full |= lane_xchg<4>(full), full |= lane_xchg<2>(full), full |= lane_xchg<1>(full);
+  float v[4];
+  int c[4], m[4], bank[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int en = lane + 64 * u, q = en % S;
+    const bool tail = q >= kf;
+    v[u] = -INFINITY, c[u] = kNone, m[u] = 0, bank[u] = -1;
+    int tok = -2, fin = 1, mj = 0;  // tok: the word whose bits count (-2: none)
+    if (en < n) {
+      const int j = en / S;
+      const int64_t r = (int64_t)j * B + i;
+      fin = e.fin_src[r], mj = e.f.met_src[r];
+      if (!tail) {
+        v[u] = cand_v[r * S + q], c[u] = cand_i[r * kf + q];
+        if (c[u] != kNone && !fin) tok = c[u] % V;
+      } else if (!fin) {
+        const int w = word[q - kf];
+        bool first = (unsigned)w < (unsigned)V;
+        for (int s = 0; s < q - kf; ++s) first = first && word[s] != w;
+        if (first) v[u] = cand_v[r * S + q], c[u] = j * V + w, tok = w;
+      }
+    }
+    int bits = 0;  // (every lane runs the broadcasts)
+    for (int s = 0; s < W; ++s) {
+      const int w = __shfl(sw, s, 64), b = __shfl(sb, s, 64);
+      bits |= w == tok ? b : 0;
+    }
+    const bool advances = (bits & ~mj) != 0;
+    bool keep = c[u] != kNone;
+    if (tail) keep = keep && advances;
+    else if (!fin) keep = keep && !advances && !(tok == e.end_id && mj != full);
+    if (keep) {
+      v[u] = v[u] == v[u] ? v[u] : -INFINITY;  // (a NaN score ranks last)
+      m[u] = mj | bits, bank[u] = __popc((unsigned)m[u]);
+    } else {
+      v[u] = -INFINITY, c[u] = kNone;
+    }
+  }
+  int taken = 0;
+  for (int round = 0; round < k && taken < k; ++round) {  // (a round with a bank left takes at least one)
+    int present = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) present |= bank[u] >= 0 ? 1 << bank[u] : 0;
+    present |= lane_xchg<32>(present), present |= lane_xchg<16>(present), present |= lane_xchg<8>(present);
+    present |= lane_xchg<4>(present), present |= lane_xchg<2>(present), present |= lane_xchg<1>(present);
+    if (!present) break;  // (the same in every lane)
+    while (present && taken < k) {
+      const int b = 31 - __clz(present);
+      present &= ~(1 << b);
+      float best = -INFINITY;
+      int bidx = kNone, bpos = -1;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (bank[u] == b && (v[u] > best || (v[u] == best && c[u] < bidx))) best = v[u], bidx = c[u], bpos = lane + 64 * u;
+      wave_best(best, bidx, bpos);
+      if (bidx == kNone) continue;
+      int mine = 0;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (bpos == lane + 64 * u) mine = m[u], bank[u] = -1;
+      const int met = __shfl(mine, bpos & 63, 64);
+      if (lane == 0) {
+        int src, tok;
+        beam_end_emit(e, taken, i, B, V, best, bidx, out_prob, out_src, out_tok, src, tok);
+        e.f.met_dst[taken * B + i] = met;
+      }
+      ++taken;
+    }
+  }
+  if (lane == 0)
+    for (; taken < k; ++taken) {  // fewer than k candidates
+      int src, tok;
+      beam_end_emit(e, taken, i, B, V, -INFINITY, kNone, out_prob, out_src, out_tok, src, tok);
+      e.f.met_dst[taken * B + i] = e.f.met_src[i];
+    }
+}
+
+template <int KM, bool ENDED = false, bool FORCED = false>
 static void beam_row_topk(const float* logits, const float* prev, int rows, int B, int V, int k, int logsm,
-                          float* cand_v, int32_t* cand_i, hipStream_t s, BeamEndArg<ENDED> e = {}) {
+                          float* cand_v, int32_t* cand_i, hipStream_t s, BeamEndArg<ENDED, FORCED> e = {}) {
   // 512 threads per row where the row fits 20 values per thread (42 vs 50 us per token at B = 1280
   // with 256 threads, round 2)
   if (V <= 512 * 20 && KM * 8 <= 64)
-    beam_row_topk_kernel<KM, 20, 512, ENDED><<<rows, 512, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i, e);
+    beam_row_topk_kernel<KM, 20, 512, ENDED, FORCED><<<rows, 512, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i, e);
   else if (V <= 256 * 40)
-    beam_row_topk_kernel<KM, 40, 256, ENDED><<<rows, 256, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i, e);
-  else beam_row_topk_kernel<KM, 0, 256, ENDED><<<rows, 256, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i, e);
+    beam_row_topk_kernel<KM, 40, 256, ENDED, FORCED><<<rows, 256, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i, e);
+  else beam_row_topk_kernel<KM, 0, 256, ENDED, FORCED><<<rows, 256, 0, s>>>(logits, prev, B, V, k, logsm, cand_v, cand_i, e);
 }
 
 static void require_beam_end(const char* who, int V, const BeamEnd& e) {
@@ -780,6 +938,20 @@ static void beam_step_launch(const BeamStep& b, BeamEndArg<ENDED> ea, hipStream_
   const BeamReorder* ro = b.reorder;
   const BeamGroups* gr = b.groups && b.groups->G > 1 ? b.groups : nullptr;
   const int k = b.k, k_in = b.k_in, B = b.B, V = b.V, rows = k_in * B, logsm = ENDED ? 1 : b.logsm;
+  if constexpr (ENDED) {
+    if (b.forced) {  // kf finalists and the slot words' scores per row, then the bank round-robin
+      const int kf = std::min(16, k + b.forced->W + 1);
+      BeamEndForced ef;
+      static_cast<BeamEnd&>(ef) = ea, ef.f = *b.forced;
+      with_km(kf, [&](auto km) {
+        beam_row_topk<decltype(km)::value, true, true>(b.logits, b.prev, rows, B, V, kf, 1, b.cand_v, b.cand_i, s, ef);
+      });
+      CAPGEN_HIP(hipGetLastError());
+      beam_forced_merge_kernel<<<B, 64, 0, s>>>(b.cand_v, b.cand_i, k_in, B, V, k, kf, b.out_prob, b.out_src, b.out_tok, ef);
+      CAPGEN_HIP(hipGetLastError());
+      return;
+    }
+  }
   with_km(k, [&](auto km) {
     constexpr int KM = decltype(km)::value;
     if (ro)
@@ -817,6 +989,15 @@ void beam_step(const BeamStep& b, hipStream_t s) {
   const BeamGroups* gr = b.groups && b.groups->G > 1 ? b.groups : nullptr;  // (one group: no groups)
   require(!gr || (e && !b.stats && !ro), "beam_step: groups need end and take neither stats nor reorder");
   require(!gr || k_in == 1 || k_in == k, "beam_step: k_in must be 1 or k with groups");
+  const BeamForced* fo = b.forced;
+  if (fo) {
+    require(e && !b.stats && !ro && !b.groups, "beam_step: forced needs end and takes none of stats, reorder and groups");
+    require(fo->W >= 1 && k + fo->W <= 15, "beam_step: beam_size + words must be <= 15, words >= 1");
+    require(k + fo->W + 1 <= V, "beam_step: beam_size + words + 1 must be <= num_vocab");
+    require(k_in <= k, "beam_step: k_in must be <= k with forced");
+    require(fo->word && fo->group && fo->met_src && fo->met_dst, "beam_step: null word / group / met");
+    require(fo->met_src != fo->met_dst, "beam_step: met must be double-buffered");
+  }
   require(!ro || b.stats, "beam_step: reorder without stats (the one-launch form selects from the slab stats)");
   require(!e || !b.stats || ro, "beam_step: end with stats but without reorder (no END-aware two-launch slab form)");
   require(!b.stats || slab_select_ok(V), "beam_step: V must be in [1, 16384] with stats");
@@ -834,7 +1015,17 @@ void beam_step(const BeamStep& b, hipStream_t s) {
           wr(b.out_src, R * 4), wr(b.out_tok, R * 4), rd(ro->seq_src, R * ro->Tw * 8), wr(ro->seq_dst, R * ro->Tw * 8),
           rd(ro->ids_src, R * ro->Tc * 4), wr(ro->ids_dst, R * ro->Tc * 4), rd(ro->kv_src, R * ro->Tc * 4),
           wr(ro->kv_dst, R * ro->Tc * 4)});
-    else {
+    else if (fo) {
+      const int64_t Wn = fo->W, kf = std::min<int64_t>(16, k + Wn + 1);
+      op(s, "beam_row_topk_forced", {rd(b.logits, Rin * V * 4), rd(b.prev, b.prev ? Rin * 4 : 0), rd(n.fin_src, Rin * 4),
+                                     rd(fo->word, b.B * Wn * 4), wr(b.cand_v, Rin * (kf + Wn) * 4),
+                                     wr(b.cand_i, Rin * kf * 4)});
+      op(s, "beam_forced_merge",
+         {rd(b.cand_v, Rin * (kf + Wn) * 4), rd(b.cand_i, Rin * kf * 4), rd(n.fin_src, Rin * 4), rd(n.len_src, Rin * 4),
+          rd(fo->word, b.B * Wn * 4), rd(fo->group, b.B * Wn * 4), rd(fo->met_src, Rin * 4), wr(b.out_prob, R * 4),
+          wr(b.out_src, R * 4), wr(b.out_tok, R * 4), wr(n.fin_dst, R * 4), wr(n.len_dst, R * 4),
+          wr(fo->met_dst, R * 4)});
+    } else {
       op(s, "beam_row_topk_ended", {rd(b.logits, Rin * V * 4), rd(b.prev, b.prev ? Rin * 4 : 0), rd(n.fin_src, Rin * 4),
                                     wr(b.cand_v, Rin * k * 4), wr(b.cand_i, Rin * k * 4)});
       op(s, gr ? "beam_group_merge" : "beam_merge_ended",
@@ -850,12 +1041,15 @@ void beam_step(const BeamStep& b, hipStream_t s) {
 // The end of the END-aware search (definition above), one wave per image, lane j = hypothesis j (k <= 16):
 // the final scores, each hypothesis' rank by counting the ones ordered before it, then the n_best rows.
 // NORM = false: alpha == 0, the score is logp itself.
-template <bool NORM>
+// MET: beam_forced's finish -- popcount(met) ranks before the score, met_out (nullable) gets the masks.
+template <bool NORM, bool MET = false>
 __global__ void __launch_bounds__(64) beam_finish_kernel(const int64_t* __restrict__ seq, const float* __restrict__ logp,
                                                          const int32_t* __restrict__ len, int k, int B, int Tw,
                                                          float alpha, int n_best, int64_t* __restrict__ ids_out,
                                                          float* __restrict__ score_out, float* __restrict__ logp_out,
-                                                         int32_t* __restrict__ len_out) {
+                                                         int32_t* __restrict__ len_out,
+                                                         const int32_t* __restrict__ met = nullptr,
+                                                         int32_t* __restrict__ met_out = nullptr) {
   __shared__ int order[16];  // order[rank] = hypothesis
   const int i = blockIdx.x, lane = threadIdx.x;
   const bool on = lane < k;
@@ -864,12 +1058,24 @@ __global__ void __launch_bounds__(64) beam_finish_kernel(const int64_t* __restri
   float sc = lp;
   if constexpr (NORM) sc = lp / powf((float)max(ln, 1), alpha);
   const float key = sc == sc ? sc : -INFINITY;  // (a NaN ranks last among equals, by beam index)
-  int rank = 0;
-  for (int j = 0; j < k; ++j) {
-    const float kj = __shfl(key, j, 64);
-    rank += (kj > key || (kj == key && j < lane)) ? 1 : 0;
+  int rank = 0, mt = 0;
+  if constexpr (MET) {
+    mt = on ? met[lane * B + i] : 0;
+    const int bank = __popc((unsigned)mt);
+    for (int j = 0; j < k; ++j) {
+      const float kj = __shfl(key, j, 64);
+      const int bj = __shfl(bank, j, 64);
+      rank += (bj > bank || (bj == bank && (kj > key || (kj == key && j < lane)))) ? 1 : 0;
+    }
+  } else {
+    for (int j = 0; j < k; ++j) {
+      const float kj = __shfl(key, j, 64);
+      rank += (kj > key || (kj == key && j < lane)) ? 1 : 0;
+    }
   }
   if (on && rank < n_best) {
+    if constexpr (MET)
+      if (met_out) met_out[rank * B + i] = mt;
     order[rank] = lane;
     if (score_out) score_out[rank * B + i] = sc;
     if (logp_out) logp_out[rank * B + i] = lp;
@@ -882,17 +1088,28 @@ __global__ void __launch_bounds__(64) beam_finish_kernel(const int64_t* __restri
   }
 }
 void beam_finish(const int64_t* seq, const float* logp, const int32_t* len, int k, int B, int Tw, float alpha,
-                 int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, hipStream_t s) {
+                 int n_best, int64_t* ids_out, float* score_out, float* logp_out, int32_t* len_out, hipStream_t s,
+                 const int32_t* met, int32_t* met_out) {
   require(k >= 1 && k <= 16, "beam_finish: beam_size must be in [1, 16]");
   require(n_best >= 1 && n_best <= k, "beam_finish: n_best must be in [1, beam_size]");
   require(alpha >= 0.f && alpha < INFINITY, "beam_finish: length_penalty must be finite and >= 0");  // (false for a NaN)
   require(B >= 1 && Tw >= 1 && seq && logp && len && ids_out, "beam_finish: need B, width >= 1 and non-null arrays");
+  require(met || !met_out, "beam_finish: met_out without met");
   if (hz::active()) {
     using namespace hz;
     const int64_t R = (int64_t)k * B, Ro = (int64_t)n_best * B;
     op(s, "beam_finish", {rd(seq, R * Tw * 8), rd(logp, R * 4), rd(len, R * 4), wr(ids_out, Ro * Tw * 8),
                           wr(score_out, score_out ? Ro * 4 : 0), wr(logp_out, logp_out ? Ro * 4 : 0),
-                          wr(len_out, len_out ? Ro * 4 : 0)});
+                          wr(len_out, len_out ? Ro * 4 : 0), rd(met, met ? R * 4 : 0),
+                          wr(met_out, met_out ? Ro * 4 : 0)});
+  }
+  if (met) {
+    if (alpha == 0.f)
+      beam_finish_kernel<false, true><<<B, 64, 0, s>>>(seq, logp, len, k, B, Tw, alpha, n_best, ids_out, score_out, logp_out, len_out, met, met_out);
+    else
+      beam_finish_kernel<true, true><<<B, 64, 0, s>>>(seq, logp, len, k, B, Tw, alpha, n_best, ids_out, score_out, logp_out, len_out, met, met_out);
+    CAPGEN_HIP(hipGetLastError());
+    return;
   }
   if (alpha == 0.f)
     beam_finish_kernel<false><<<B, 64, 0, s>>>(seq, logp, len, k, B, Tw, alpha, n_best, ids_out, score_out, logp_out, len_out);

@@ -243,6 +243,37 @@ int capgen_beam_diverse(capgen_t* h, const void* feats, int feats_dtype, const f
                         int32_t* len_out,   /* [num_groups*n_best*B], nullable */
                         void* stream);
 
+/* Forced-word beam search (constrained beam search, Anderson et al. 2017; the fixed-beam bank form of Post &
+ * Vilar 2018 / Hu et al. 2019): capgen_beam_nbest over captions that must contain given words.  Image i has W
+ * slots (word[i * W + s], group[i * W + s]); word = -1 is an empty slot, a group (in [0, 16)) is a set of
+ * alternative words and is met once the hypothesis has appended any of them; a word may sit in several groups.
+ * Every hypothesis carries met, the bitmask of the groups it has met.  A live hypothesis may not append <END>
+ * while a group of its image is unmet.  At every position the candidates fall into banks by popcount(met') and
+ * are ranked within their bank by (score descending, flat index ascending); the k first under (rank ascending,
+ * bank descending) are kept: the best of the highest non-empty bank, the best of the next, ..., then the second
+ * best of each.  Scores are never compared across banks, and logp stays the sum of the model's token
+ * log-probabilities.  At the end the n_best per image under (popcount(met) descending, logp / max(len, 1)^
+ * length_penalty descending, beam ascending) come back, with met in met_out: nothing is forced as max_length
+ * approaches, so a returned hypothesis may have groups unmet -- met says which.  Decode constraints apply as to
+ * capgen_beam_nbest.  Either dtype selects with the full-row top-k, one bank-merge launch and the three reorder
+ * launches per token.  Definition: csrc/select.hip.
+ * W = 0 (word / group unread) is capgen_beam_nbest bit for bit (the same launches), met_out zeroed.  Else
+ * beam_size + W <= 15 and beam_size + W + 1 <= num_vocab; word in [0, num_vocab) or -1, and not end_id, 0 or 1
+ * (the caller's rule: the arrays are on the device and are not read by the host; a slot out of range is taken
+ * as empty); the rest as capgen_beam_nbest.
+ * Added without a change of CAPGEN_ABI_VERSION: no existing entry changed (backward compatible). */
+int capgen_beam_forced(capgen_t* h, const void* feats, int feats_dtype, const float* pos, int B, int N,
+                       int beam_size, int end_id, float length_penalty, int n_best,
+                       const int32_t* word,   /* device [B, W] */
+                       const int32_t* group,  /* device [B, W] */
+                       int W,
+                       int64_t* ids_out,   /* [n_best*B, max_length] */
+                       float* score_out,   /* [n_best*B], nullable */
+                       float* logp_out,    /* [n_best*B], nullable */
+                       int32_t* len_out,   /* [n_best*B], nullable */
+                       int32_t* met_out,   /* [n_best*B], nullable */
+                       void* stream);
+
 /* Sampled decoding: n_samples captions per image drawn from the model's distribution, one encoder
  * pass, KV-cached.  Position t draws token ~ softmax(logits / temperature) restricted to the top_k
  * largest logits (top_k = 0: the whole vocabulary) by Gumbel-max over the counter hash of (seed,
@@ -329,6 +360,13 @@ int capgen_ensemble_beam_diverse(const capgen_ensemble* e, const void* feats, in
                                  int N, int beam_size, int num_groups, float diversity_penalty, int end_id,
                                  float length_penalty, int n_best, int64_t* ids_out, float* score_out,
                                  float* logp_out, int32_t* len_out, void* stream);
+
+/* capgen_beam_forced over the ensemble's distribution: its arguments after h.
+ * Added without a change of CAPGEN_ABI_VERSION: no existing entry changed (backward compatible). */
+int capgen_ensemble_beam_forced(const capgen_ensemble* e, const void* feats, int feats_dtype, const float* pos, int B,
+                                int N, int beam_size, int end_id, float length_penalty, int n_best, const int32_t* word,
+                                const int32_t* group, int W, int64_t* ids_out, float* score_out, float* logp_out,
+                                int32_t* len_out, int32_t* met_out, void* stream);
 
 /* Decode scoring of capgen_greedy / capgen_beam: 0 (default) = Transformer (argmax of Softmax,
  * beams accumulate probabilities, model.py:124-128,183); 1 = PolicyNetwork, the SCST model
@@ -686,6 +724,16 @@ int capgen_debug_beam_group_step(const float* logits, const float* prev, int k_i
                                  int num_groups, float diversity_penalty, int end_id, const int32_t* fin_src,
                                  const int32_t* len_src, int32_t* fin_dst, int32_t* len_dst, float* cand_v,
                                  int32_t* cand_i, float* out_prob, int32_t* out_src, int32_t* out_tok, void* stream);
+/* One step of capgen_beam_forced's selection (definition: csrc/select.hip): the full-row END-aware top-k with
+ * kf = min(16, k + W + 1) finalists and the W slot words' scores per row, then the bank merge.  k_in <= k;
+ * word / group: device [B][W]; met_src [k_in * B] / met_dst [k * B] like fin / len; cand_v: k_in * B * (kf + W)
+ * floats, cand_i: k_in * B * kf.  With no word on any image (W = 0, or every slot -1: the hook reads the slots on the
+ * host) it launches capgen_debug_beam_step_ended's full-row form, whatever k <= 16, and zeroes met_dst. */
+int capgen_debug_beam_forced_step(const float* logits, const float* prev, int k_in, int B, int V, int k, int end_id,
+                                  const int32_t* word, const int32_t* group, int W, const int32_t* fin_src,
+                                  const int32_t* len_src, const int32_t* met_src, int32_t* fin_dst, int32_t* len_dst,
+                                  int32_t* met_dst, float* cand_v, int32_t* cand_i, float* out_prob, int32_t* out_src,
+                                  int32_t* out_tok, void* stream);
 /* The end of capgen_beam_nbest: the n_best of the k hypotheses (rows j * B + i of seq [k * B][Tw], logp, len)
  * per image by logp / max(len, 1)^length_penalty -> ids_out [n_best * B][Tw], score / logp / len (nullable). */
 int capgen_debug_beam_finish(const int64_t* seq, const float* logp, const int32_t* len, int k, int B, int Tw,

@@ -20,6 +20,11 @@ diversity_penalty 0.5), both with <END> = id 2, length_penalty 0 and n_best 1 (p
 beam6g3 selects with the full-row top-k, the group merge and the three reorder launches per token where bf16
 beam6 takes one fused launch, so it is read against beam6 of the same run.  --dtype fp32 runs every mode on the
 fp32 engine.
+beam5f2: forced-word beam search (Engine.beam_forced) at beam 5 with two single-word groups per image, the words
+drawn from a fixed seed (ids 3 .. num_vocab - 1, two distinct per image), <END> = id 2, length_penalty 0, n_best 1:
+beam5e's decoder steps; the selection is the full-row top-k with 8 finalists and 2 word scores per row, the bank
+merge and the three reorder launches per token where bf16 beam5e takes one fused launch, so it is read against
+beam5e of the same run.
 
 Algorithmic work (KV-cached count): beam-5 1776.7 GFLOP, greedy 699.4 GFLOP per
 256-image batch.  The reference CPU path (no KV cache) took 25.0 s (beam) / 5.87 s (greedy) per
@@ -32,6 +37,7 @@ import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "image-caption_amd"))
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from capgen import _lib, preset  # noqa: E402
@@ -43,6 +49,7 @@ GFLOP = {"beam5": 1776.7, "greedy": 699.4, "sample1": 699.4, "sample5": 1776.7, 
          "sample1p": 699.4, "sample5p": 1776.7, "beam5e": 1776.7, "beam5en": 1776.7,
          "beam5ec": 1776.7, "sample1c": 699.4,
          "beam6": 2046.0, "beam6g3": 2046.0,  # (beam5 + one more row's decoder steps: (1776.7 - 699.4) / 4)
+         "beam5f2": 1776.7,
          "ens2_beam5e": 2 * 1776.7, "ens3_beam5e": 3 * 1776.7, "ens2_sample1": 2 * 699.4}  # (every member's steps)
 
 
@@ -52,7 +59,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1, help="untimed calls first (the first one tunes GEMM shapes and sizes the workspaces)")
     ap.add_argument("--modes", default="beam5,greedy", help="of beam5, greedy, sample1, sample5, sample1p, sample5p, beam5e, beam5en, beam5ec, sample1c, "
-                    "ens2_beam5e, ens3_beam5e, ens2_sample1, beam6, beam6g3")
+                    "ens2_beam5e, ens3_beam5e, ens2_sample1, beam6, beam6g3, beam5f2")
     ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp32"))
     args = ap.parse_args()
     cfg = preset("C2", dtype=args.dtype)
@@ -76,6 +83,9 @@ def main():
                               cfg.num_vocab, seed=7)
     f = f.to(dev, torch.bfloat16 if args.dtype == "bf16" else torch.float32).contiguous()
     p = p.to(dev).contiguous()
+    rng = np.random.default_rng(11)  # beam5f2's words: two per image, each its own group
+    f2_word = np.stack([rng.choice(np.arange(3, cfg.num_vocab), 2, replace=False) for _ in range(B)]).astype(np.int32)
+    f2_group = np.tile(np.arange(2, dtype=np.int32), (B, 1))
     runs = {"beam5": lambda: eng.beam(f, p, 5), "greedy": lambda: eng.greedy(f, p, want_attention=False),
             "sample1": lambda: eng.sample(f, p, n_samples=1, seed=1), "sample5": lambda: eng.sample(f, p, n_samples=5, seed=1),
             "sample1p": lambda: eng.sample(f, p, n_samples=1, seed=1, top_p=0.9),
@@ -86,6 +96,7 @@ def main():
             "sample1c": lambda: eng.sample(f, p, n_samples=1, seed=1),
             "beam6": lambda: eng.beam_nbest(f, p, 6, 2, length_penalty=0.0, n_best=1),
             "beam6g3": lambda: eng.beam_diverse(f, p, 6, 3, 0.5, 2, length_penalty=0.0, n_best=1),
+            "beam5f2": lambda: eng.beam_forced(f, p, 5, 2, f2_word, f2_group, length_penalty=0.0, n_best=1),
             "ens2_beam5e": lambda: ensemble_beam_nbest(ensemble(2), f, p, 5, 2, length_penalty=0.0, n_best=1),
             "ens3_beam5e": lambda: ensemble_beam_nbest(ensemble(3), f, p, 5, 2, length_penalty=0.0, n_best=1),
             "ens2_sample1": lambda: ensemble_sample(ensemble(2), f, p, n_samples=1, seed=1)}
